@@ -12,7 +12,12 @@ partial sums stay on the device and are SUM-all-reduced across ranks once (RCCL 
 xGMI) at the end of the timed region (distributed.ObjectiveAccumulator), so no
 collective sits on a step's critical path.
 
-Side legs in the same JSON line (not the headline):
+A plain run (--gpus / --steps / --warmup only) does just that: set up, warm up, time the K
+steps, print the result line. --dump-outputs DIR also writes what the last timed step
+computed (dump_outputs below), so two builds can be compared output for output: the inputs
+are seeded and identical from run to run.
+
+Side legs, only with --full, in the same JSON line (not the headline):
   variational  BASELINE configs[4] per GPU: DeepGP variational path B=1024 N=256 M=64
                D=32 -- shared K_ZZ factor (gpk_kzz_chol_f64) + column-tiled predictive
                mean / variance / ELL (gpk_variational_f32), and the fused adjoint
@@ -29,7 +34,7 @@ Side legs in the same JSON line (not the headline):
                variational path; and the MLL relative error of the GPU kernel vs the
                fp64 oracle on a window sample (parity unpinned vs GPyTorch: DESIGN §2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -111,6 +116,25 @@ def make_inputs(B, N, D, device, seed):
     X = (torch.randn(B, N, D, generator=g) / math.sqrt(D)).to(device)
     y = torch.randn(B, N, generator=torch.Generator().manual_seed(seed + 1)).to(device)
     return X, y
+
+
+DUMP_L_BYTES = 32 << 20    # --dump-outputs: the share of L kept (the whole dump stays < 64 MB)
+
+
+def dump_outputs(path, mll, info, L):
+    """--dump-outputs: what the caller of the last timed step received (ops.ExactMLLOut of the
+    headline launch) as float32 .npy files: mll (B,), info (B,) and L (n, N, N) for a fixed,
+    seeded sample of n windows (all of them if they fit DUMP_L_BYTES), whose window numbers
+    are in L_windows."""
+    os.makedirs(path, exist_ok=True)
+    B, N = L.shape[0], L.shape[1]
+    n = max(1, min(B, DUMP_L_BYTES // (4 * N * N)))
+    idx = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    np.save(os.path.join(path, "mll.npy"), mll.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "info.npy"), info.cpu().numpy().astype(np.float32))
+    Ls = L[torch.as_tensor(idx, device=L.device)]
+    np.save(os.path.join(path, "L.npy"), Ls.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "L_windows.npy"), idx.astype(np.float32))
 
 
 def time_launches(fn, n):
@@ -398,6 +422,13 @@ def main():
     ap.add_argument("--N", type=int, default=256)
     ap.add_argument("--D", type=int, default=32)
     ap.add_argument("--strong", action="store_true", help="B is the global batch, sharded over ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (variational, backward, posterior, cfg 2, N=800, "
+                         "variant build, end-to-end step, CPU baselines and oracle comparisons); "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (mll, info, a seeded "
+                         "sample of L) to DIR/<name>.npy (rank 0)")
     ap.add_argument("--var-B", type=int, default=1024)
     ap.add_argument("--var-N", type=int, default=256)
     ap.add_argument("--var-M", type=int, default=64)
@@ -419,6 +450,9 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="every rank uses cuda:0 (tests/test_world2_gpu.py: two ranks on one GPU)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: nothing but the headline's timed steps
+        args.no_var = args.no_var3 = args.no_cpu_baseline = args.no_grad = args.no_e2e = True
+        args.no_cfg2 = args.no_large = args.no_variants = True
 
     rank, local, world = env_rank_world()
     if world != args.gpus and world == 1 and args.gpus > 1:
@@ -504,6 +538,8 @@ def main():
     elapsed = t1 - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps
     ops.check_cholesky_info(info, 1e-6, inputs=(X,))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, acc.rows[args.steps - 1], info, Lbuf)
     rank_times = None
     if pg:
         t = torch.tensor([elapsed, kern_ms], device=dev, dtype=torch.float64)
@@ -514,7 +550,7 @@ def main():
         elapsed, kern_ms = (float(v) for v in t.tolist())
     mean_mll = float(totals[-1].item()) / B_total
     eager_kern_ms = None
-    if graph is not None:   # the eager loop beside the graph replay (same launches)
+    if graph is not None and args.full:   # the eager loop beside the graph replay (same launches)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -523,7 +559,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         eager_kern_ms = e0.elapsed_time(e1) / args.steps
-    else:                   # the timed loop itself was the eager one
+    elif graph is None:     # the timed loop itself was the eager one
         eager_kern_ms = kern_ms
 
     # 256 < N <= 800 (GPyTorch's Cholesky regime, the blocked kernels of gpk_exact_large.hip):
