@@ -73,6 +73,19 @@ SIGNATURES = {
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, c_void_p]),
+    "gpk_kzz_chol_f64_batched": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_float, c_double,
+                                         c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_kzz_backward_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gpk_kzz_backward_f64_batched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_variational_batched_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_variational_adjoint_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gpk_variational_adjoint_batched_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                                    c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p]),
     "gpk_window_gather_f32": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }

@@ -7,7 +7,7 @@
 
 extern "C" {
 
-int gpk_version(void) { return 100; }
+int gpk_version(void) { return 200; }
 
 const char* gpk_strerror(int code) {
   if (code == 0) return "success";
@@ -342,6 +342,107 @@ int gpk_variational_adjoint_f32(const float* X, const float* Z, const double* Li
   if (dZ == nullptr) return -16;
   if (dpar == nullptr) return -17;
   GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar};
+  return gpk_launch_var_adjoint(a, (hipStream_t)stream);
+}
+
+// ---- multi-output (batched) variational chain: output o on grid dimension y of every launch
+constexpr int kGpkMaxOutputs = 65535;   // gridDim.y
+
+int gpk_kzz_chol_f64_batched(const float* Z, const float* hyp, int O, int M, int D, float jitter,
+                             double chol_jitter, int max_tries, double* L, double* Linv, int* info,
+                             void* stream) {
+  if (Z == nullptr) return -1;
+  if (hyp == nullptr) return -2;
+  if (O < 1 || O > kGpkMaxOutputs) return -3;
+  if (M < 1 || M > 256) return -4;
+  if (D < 1 || D > 64) return -5;
+  if (max_tries < 0 || max_tries > 12) return -8;
+  if (L == nullptr) return -9;
+  if (Linv == nullptr) return -10;
+  if (info == nullptr) return -11;
+  GpkKzzArgs a{Z, hyp, M, D, jitter, chol_jitter, max_tries, L, Linv, info, O};
+  return gpk_launch_kzz16(a, (hipStream_t)stream);
+}
+
+size_t gpk_kzz_backward_batched_workspace_bytes(int O, int M, int D) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_kzz_backward_workspace_bytes(M, D);
+}
+
+int gpk_kzz_backward_f64_batched(const double* dLinv, const double* L, const double* Linv,
+                                 const float* Z, const float* hyp, int O, int M, int D, void* workspace,
+                                 float* dZ, float* dhyp, void* stream) {
+  if (dLinv == nullptr) return -1;
+  if (L == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (Z == nullptr) return -4;
+  if (hyp == nullptr) return -5;
+  if (O < 1 || O > kGpkMaxOutputs) return -6;
+  if (M < 1 || M > 256) return -7;
+  if (D < 1 || D > 64) return -8;
+  if (workspace == nullptr) return -9;
+  if (dZ == nullptr) return -10;
+  if (dhyp == nullptr) return -11;
+  GpkKzzGradArgs a{dLinv, L, Linv, Z, hyp, M, D, workspace, dZ, dhyp, O};
+  return gpk_launch_kzz_grad(a, (hipStream_t)stream);
+}
+
+int gpk_variational_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                const float* vmean, const float* vstd, const float* hyp, int O, int B,
+                                int N, int M, int D, float* mean, float* var, int* flags, void* saved,
+                                void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vmean == nullptr) return -5;
+  if (vstd == nullptr) return -6;
+  if (hyp == nullptr) return -7;
+  if (O < 1 || O > kGpkMaxOutputs) return -8;
+  if (B < 0) return -9;
+  if (N < 1) return -10;
+  if (M < 1 || M > 256) return -11;
+  if (D < 1 || D > 64) return -12;
+  if (mean == nullptr) return -13;
+  if (var == nullptr) return -14;
+  if (saved != nullptr && (B < 1 || gpk_var_saved_bytes(B, N, M, D) == 0)) return -16;
+  if (B == 0) return 0;
+  GpkVarArgs a{X, Z, Linv, vmean, vstd, hyp, nullptr, B, N, M, D, mean, var, nullptr, (float*)saved, O,
+               shared_x ? 0LL : (long long)B * N * D};
+  return gpk_launch_var(a, flags, (hipStream_t)stream);
+}
+
+size_t gpk_variational_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D, int has_saved) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * (has_saved ? gpk_variational_adjoint_saved_workspace_bytes(B, N, M, D)
+                                : gpk_variational_adjoint_workspace_bytes(B, N, M, D));
+}
+
+int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                        const float* vmean, const float* vstd, const float* hyp,
+                                        const float* gmean, const float* gvar, const void* saved, int O,
+                                        int B, int N, int M, int D, void* workspace, float* dX,
+                                        double* dLinv, float* dZ, float* dpar, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vmean == nullptr) return -5;
+  if (vstd == nullptr) return -6;
+  if (hyp == nullptr) return -7;
+  if (gmean == nullptr) return -8;
+  if (gvar == nullptr) return -9;
+  if (O < 1 || O > kGpkMaxOutputs) return -11;
+  if (B < 1) return -12;
+  if (N < 1) return -13;
+  if (M < 1 || M > 256) return -14;
+  if (D < 1 || D > 64) return -15;
+  if (saved != nullptr && gpk_var_saved_bytes(B, N, M, D) == 0) return -10;
+  if (workspace == nullptr) return -16;
+  if (dX == nullptr) return -17;
+  if (dLinv == nullptr) return -18;
+  if (dZ == nullptr) return -19;
+  if (dpar == nullptr) return -20;
+  GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar,
+                  (const float*)saved, O, shared_x ? 0LL : (long long)B * N * D};
   return gpk_launch_var_adjoint(a, (hipStream_t)stream);
 }
 

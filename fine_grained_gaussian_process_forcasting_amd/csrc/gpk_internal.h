@@ -46,6 +46,7 @@ struct GpkKzzArgs {
   double* L;           // (M, M) out
   double* Linv;        // (M, M) out
   int* info;           // (1,) out
+  int O = 1;           // outputs (independent GPs), dense: Z (O, M, D), hyp (O, 1 + D), L / Linv (O, M, M), info (O,)
 };
 
 struct GpkVarArgs {
@@ -61,6 +62,18 @@ struct GpkVarArgs {
   float* var;          // (B, N)
   float* ell;          // (B,) or nullptr: sum_i expected log prob
   float* saved;        // training: gpk_var_saved_bytes(B, N, M, D) bytes of state for the adjoint, or nullptr
+  int O = 1;           // outputs, on grid dimension y: every array above gains a leading dense O ...
+  long long x_stride = 0;  // ... but X: elements between two outputs' inputs, 0 = one (B, N, D) shared by all
+};
+
+// Per-output strides a batched launch hands its kernels (workgroup blockIdx.y = output o offsets
+// its base pointers, then runs the single-output body). What M and D determine (Z, Linv, vmean,
+// vstd, hyp, dZ, dLinv, dpar) the kernels derive themselves.
+struct GpkOStr {
+  long long x;    // X elements (0: shared inputs)
+  long long bn;   // B * N: mean, var, gmean, gvar (dX: bn * D)
+  long long sv;   // floats of saved state per output
+  long long ws;   // floats of workspace per output (a multiple of 64; fp64 slices: ws / 2 doubles)
 };
 
 struct GpkVarAdjArgs {
@@ -79,6 +92,8 @@ struct GpkVarAdjArgs {
   float* dZ;           // (M, D) out: the K_ZX part of dZ
   float* dpar;         // (2M + 2D + 2) out: dvmean, dvstd, ds2, dlengthscale, dweights, dbias
   const float* saved;  // the training forward's state (gpk_var_saved_bytes), or nullptr: recompute
+  int O = 1;           // outputs, as GpkVarArgs: dense leading O on every array (ws: O slices), X by x_stride
+  long long x_stride = 0;
 };
 
 
@@ -92,6 +107,7 @@ struct GpkKzzGradArgs {
   void* ws;            // gpk_kzz_grad_ws_bytes(M, D) bytes
   float* dZ;           // (M, D) out
   float* dhyp;         // (1 + D) out: {ds2, dlengthscale[D]}
+  int O = 1;           // outputs: dense leading O on every array, ws O slices of gpk_kzz_grad_ws_bytes
 };
 
 size_t gpk_kzz_grad_ws_bytes(int M, int D);

@@ -352,6 +352,14 @@ gpk_kzz16_kernel(const float* __restrict__ Z, const float* __restrict__ hyp, int
                  float jitter_var, double jitter_chol, int max_tries, double* __restrict__ L,
                  double* __restrict__ Linv, int* __restrict__ info) {
   extern __shared__ __attribute__((aligned(16))) double dsm[];
+  {   // output blockIdx.y of a batched launch: dense (O, ...) arrays, its own ladder and info word
+    const size_t o = blockIdx.y;
+    Z += o * (size_t)(M * D);
+    hyp += o * (size_t)(1 + D);
+    L += o * (size_t)(M * M);
+    Linv += o * (size_t)(M * M);
+    info += o;
+  }
   const int T = (M + 15) >> 4;
   double* panel = dsm;                 // (T - 1) tiles x 256, [slot][reg][lane]
   double* dbuf = panel + (size_t)(T > 1 ? T - 1 : 1) * 256;   // 2 x 256: hand-over tiles (t, t)
@@ -657,6 +665,12 @@ gpk_kzz_inv_kernel(const double* __restrict__ L, int M, const int* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) double dsm[];
   const int Mp = (M + 15) & ~15, T16 = Mp >> 4;
   const int jb = blockIdx.x;
+  {   // output blockIdx.y of a batched launch (T x O workgroups)
+    const size_t o = blockIdx.y;
+    L += o * (size_t)(M * M);
+    Linv += o * (size_t)(M * M);
+    info += o;
+  }
   const int nb = T16 - jb;            // block rows jb .. T16-1 of this block column
   double* Tv = dsm;                   // nb tiles: T_{jb+u}, row-major [row][col], row stride 17
   double* Xs = Tv + T16 * kInvTile;   // nb x 256: X_{jb+u}, row-major
@@ -808,12 +822,12 @@ int launch_kzz16(const GpkKzzArgs& a, hipStream_t stream) {
                      kKfWords * sizeof(int) + (size_t)(a.M * kzz_zstride(a.D) + a.M + a.D) * sizeof(float);
   if (lds > 160 * 1024) return -4;
   set_lds_once<gpk_kzz16_kernel<NS>>();
-  hipLaunchKernelGGL((gpk_kzz16_kernel<NS>), dim3(1), dim3(KT), lds, stream, a.Z, a.hyp, a.M, a.D,
+  hipLaunchKernelGGL((gpk_kzz16_kernel<NS>), dim3(1, a.O), dim3(KT), lds, stream, a.Z, a.hyp, a.M, a.D,
                      a.jitter_var, a.jitter_chol, a.max_tries, a.L, a.Linv, a.info);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   set_lds_once<gpk_kzz_inv_kernel>();
-  hipLaunchKernelGGL(gpk_kzz_inv_kernel, dim3(T), dim3(KIT), kzz_inv_lds_bytes(T), stream, a.L, a.M,
+  hipLaunchKernelGGL(gpk_kzz_inv_kernel, dim3(T, a.O), dim3(KIT), kzz_inv_lds_bytes(T), stream, a.L, a.M,
                      a.info, a.Linv);
   e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

@@ -44,6 +44,12 @@ GPK_DEVICE void tri_tile(int t, int& it, int& jt) {
 // MODE 3: C = Phi(L^T Lbar)   A(i,k) = L[k][i]             B(k,j) = Lbar[k][j]   kb in [ib, T)           lower, diag / 2
 // MODE 4: C = P Linv          A(i,k) = P[i][k]             B(k,j) = Linv[k][j]   kb in [jb, ib]          lower
 // MODE 5: C = Linv^T U        A(i,k) = Linv[k][i]          B(k,j) = U[k][j]      kb in [max(ib,jb), T)   full
+// doubles between two outputs' operands of a batched launch (a caller's (O, M, M) array or a
+// workspace slice)
+struct KzzGemmStr {
+  long long a, b, c;
+};
+
 template <int MODE>
 struct KzzGemm {
   static constexpr bool kFull = MODE == 1 || MODE == 5;
@@ -57,9 +63,15 @@ struct KzzGemm {
 template <int MODE>
 __global__ void __launch_bounds__(256)
 gpk_kzzg_gemm_kernel(const double* __restrict__ Am, const double* __restrict__ Bm, int M,
-                     double* __restrict__ C) {
+                     double* __restrict__ C, KzzGemmStr bs) {
   using G = KzzGemm<MODE>;
   __shared__ double red[3][256];
+  {   // output blockIdx.y of a batched launch
+    const size_t o = blockIdx.y;
+    Am += o * bs.a;
+    Bm += o * bs.b;
+    C += o * bs.c;
+  }
   const int T = (M + 15) >> 4;
   const int t = blockIdx.x;
   int ib, jb;
@@ -132,7 +144,15 @@ gpk_kzzg_gemm_kernel(const double* __restrict__ Am, const double* __restrict__ B
 constexpr int kRbfMaxD = 64;
 __global__ void __launch_bounds__(64)
 gpk_kzzg_rbf_kernel(const double* __restrict__ S, const float* __restrict__ Z,
-                    const float* __restrict__ hyp, int M, int D, double* __restrict__ part) {
+                    const float* __restrict__ hyp, int M, int D, double* __restrict__ part,
+                    long long ws_stride) {
+  {   // output blockIdx.y of a batched launch (S and part: workspace slices)
+    const size_t o = blockIdx.y;
+    S += o * ws_stride;
+    part += o * ws_stride;
+    Z += o * (size_t)(M * D);
+    hyp += o * (size_t)(1 + D);
+  }
   __shared__ double zi[16][kRbfMaxD + 1];
   __shared__ double zj[16][kRbfMaxD + 1];
   __shared__ double w[16][17];
@@ -192,7 +212,15 @@ gpk_kzzg_rbf_kernel(const double* __restrict__ S, const float* __restrict__ Z,
 __global__ void __launch_bounds__(256)
 gpk_kzzg_rows_kernel(const double* __restrict__ part, const float* __restrict__ Z,
                      const float* __restrict__ hyp, int M, int D, float* __restrict__ dZ,
-                     double* __restrict__ rpart) {
+                     double* __restrict__ rpart, long long ws_stride) {
+  {   // output blockIdx.y of a batched launch
+    const size_t o = blockIdx.y;
+    part += o * ws_stride;
+    rpart += o * ws_stride;
+    Z += o * (size_t)(M * D);
+    hyp += o * (size_t)(1 + D);
+    dZ += o * (size_t)(M * D);
+  }
   __shared__ double cs[16][kRbfMaxD + 1];
   __shared__ double w1s[16];
   const int T = (M + 15) >> 4;
@@ -243,7 +271,13 @@ gpk_kzzg_rows_kernel(const double* __restrict__ part, const float* __restrict__ 
 // over the blocks in a fixed order. One wave per output group.
 __global__ void __launch_bounds__(128)
 gpk_kzzg_fin_kernel(const double* __restrict__ rpart, const float* __restrict__ hyp, int M, int D,
-                    float* __restrict__ dhyp) {
+                    float* __restrict__ dhyp, long long ws_stride) {
+  {   // output blockIdx.y of a batched launch
+    const size_t o = blockIdx.y;
+    rpart += o * ws_stride;
+    hyp += o * (size_t)(1 + D);
+    dhyp += o * (size_t)(1 + D);
+  }
   const int e = threadIdx.x;
   if (e > D) return;
   const int T = (M + 15) >> 4;
@@ -257,10 +291,11 @@ gpk_kzzg_fin_kernel(const double* __restrict__ rpart, const float* __restrict__ 
 }
 
 template <int MODE>
-hipError_t launch_gemm(const double* A, const double* B, int M, double* C, hipStream_t stream) {
+hipError_t launch_gemm(const double* A, const double* B, int M, double* C, int O, KzzGemmStr bs,
+                       hipStream_t stream) {
   const int T = (M + 15) >> 4;
   const int ntile = KzzGemm<MODE>::kFull ? T * T : T * (T + 1) / 2;
-  hipLaunchKernelGGL((gpk_kzzg_gemm_kernel<MODE>), dim3(ntile), dim3(256), 0, stream, A, B, M, C);
+  hipLaunchKernelGGL((gpk_kzzg_gemm_kernel<MODE>), dim3(ntile, O), dim3(256), 0, stream, A, B, M, C, bs);
   return hipGetLastError();
 }
 
@@ -277,19 +312,22 @@ int gpk_launch_kzz_grad(const GpkKzzGradArgs& a, hipStream_t stream) {
   double* b1 = b0 + (size_t)M * M;
   double* part = b1 + (size_t)M * M;
   hipError_t e;
-  if ((e = launch_gemm<1>(a.dLinv, a.Linv, M, b0, stream)) != hipSuccess) return (int)e;   // T1
-  if ((e = launch_gemm<2>(a.Linv, b0, M, b1, stream)) != hipSuccess) return (int)e;        // Lbar
-  if ((e = launch_gemm<3>(a.L, b1, M, b0, stream)) != hipSuccess) return (int)e;           // P
-  if ((e = launch_gemm<4>(b0, a.Linv, M, b1, stream)) != hipSuccess) return (int)e;        // U
-  if ((e = launch_gemm<5>(a.Linv, b1, M, b0, stream)) != hipSuccess) return (int)e;        // S
+  // output o (grid dimension y) works in workspace slice o: every launch once for all outputs
+  const int O = a.O;
+  const long long mm = (long long)M * M, ws = (long long)(gpk_kzz_grad_ws_bytes(M, D) / sizeof(double));
+  if ((e = launch_gemm<1>(a.dLinv, a.Linv, M, b0, O, {mm, mm, ws}, stream)) != hipSuccess) return (int)e;   // T1
+  if ((e = launch_gemm<2>(a.Linv, b0, M, b1, O, {mm, ws, ws}, stream)) != hipSuccess) return (int)e;        // Lbar
+  if ((e = launch_gemm<3>(a.L, b1, M, b0, O, {mm, ws, ws}, stream)) != hipSuccess) return (int)e;           // P
+  if ((e = launch_gemm<4>(b0, a.Linv, M, b1, O, {ws, mm, ws}, stream)) != hipSuccess) return (int)e;        // U
+  if ((e = launch_gemm<5>(a.Linv, b1, M, b0, O, {mm, ws, ws}, stream)) != hipSuccess) return (int)e;        // S
   const int T = (M + 15) >> 4;
-  hipLaunchKernelGGL(gpk_kzzg_rbf_kernel, dim3(T * T), dim3(64), 0, stream, b0, a.Z, a.hyp, M, D, part);
+  hipLaunchKernelGGL(gpk_kzzg_rbf_kernel, dim3(T * T, O), dim3(64), 0, stream, b0, a.Z, a.hyp, M, D, part, ws);
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   double* rpart = part + (size_t)T * M * (D + 1);
-  hipLaunchKernelGGL(gpk_kzzg_rows_kernel, dim3(T), dim3(256), 0, stream, part, a.Z, a.hyp, M, D, a.dZ,
-                     rpart);
+  hipLaunchKernelGGL(gpk_kzzg_rows_kernel, dim3(T, O), dim3(256), 0, stream, part, a.Z, a.hyp, M, D, a.dZ,
+                     rpart, ws);
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(gpk_kzzg_fin_kernel, dim3(1), dim3(128), 0, stream, rpart, a.hyp, M, D, a.dhyp);
+  hipLaunchKernelGGL(gpk_kzzg_fin_kernel, dim3(1, O), dim3(128), 0, stream, rpart, a.hyp, M, D, a.dhyp, ws);
   e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

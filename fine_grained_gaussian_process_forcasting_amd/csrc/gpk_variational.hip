@@ -42,6 +42,20 @@ constexpr float kNHalfLog2e = -0.72134752044448170f;  // -0.5 * log2(e)
 
 #define GPK_HOST_DEVICE_INLINE __host__ __device__ __forceinline__
 
+// Batched (multi-output) launches: workgroup blockIdx.y = output o moves its base pointers to
+// the output's slices before the single-output body runs (scalar adds, once per workgroup).
+// GPK_O_MODEL: the inputs and the arrays M and D size; GPK_O_ADD: a pointer by an element
+// stride; GPK_O_OPT: an optional one (a null pointer stays null).
+#define GPK_O_MODEL()                                  \
+  X += (size_t)blockIdx.y * bs.x;                      \
+  Z += (size_t)blockIdx.y * (size_t)(M * D);           \
+  vmean += (size_t)blockIdx.y * (size_t)M;             \
+  vstd += (size_t)blockIdx.y * (size_t)M;              \
+  hyp += (size_t)blockIdx.y * (size_t)(4 + 2 * D)
+#define GPK_O_ADD(p, stride) (p) += (size_t)blockIdx.y * (size_t)(stride)
+#define GPK_O_OPT(p, stride) \
+  if ((p) != nullptr) (p) += (size_t)blockIdx.y * (size_t)(stride)
+
 GPK_DEVICE f64x4 mfma64(double a, double b, f64x4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
@@ -306,7 +320,11 @@ gpk_var_fwd_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                    const double* __restrict__ Linv, const float* __restrict__ vmean,
                    const float* __restrict__ vstd, const float* __restrict__ hyp, int N, int M,
                    int D, int nchunks, float* __restrict__ mean_out, float* __restrict__ var_out,
-                   int* __restrict__ flags) {
+                   int* __restrict__ flags, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(mean_out, bs.bn);
+  GPK_O_ADD(var_out, bs.bn);
   using G = VarGeo<MB>;
   constexpr int TW = G::TW, MP = G::MP;
   extern __shared__ __attribute__((aligned(16))) float vsm[];
@@ -521,7 +539,12 @@ gpk_var_fwd_l_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                      const double* __restrict__ Linv, const float* __restrict__ vmean,
                      const float* __restrict__ vstd, const float* __restrict__ hyp, int N, int M,
                      int D, int nchunks, float* __restrict__ mean_out, float* __restrict__ var_out,
-                     int* __restrict__ flags, float* __restrict__ saved) {
+                     int* __restrict__ flags, float* __restrict__ saved, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(mean_out, bs.bn);
+  GPK_O_ADD(var_out, bs.bn);
+  GPK_O_OPT(saved, bs.sv);
   using G = LGeo<MB, DQ>;
   constexpr int NWV = G::NWV, NT = G::NT, DS = G::DS, NPASS = G::NPASS, DV = G::DV;
   extern __shared__ __attribute__((aligned(16))) float vsm[];
@@ -757,7 +780,15 @@ gpk_var_adj_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                    const float* __restrict__ vstd, const float* __restrict__ hyp,
                    const float* __restrict__ gmean, const float* __restrict__ gvar, int N, int M,
                    int D, int nchunks, long long BN, float* __restrict__ wsdA, float* __restrict__ wsK,
-                   float* __restrict__ wspart, float* __restrict__ dX) {
+                   float* __restrict__ wspart, float* __restrict__ dX, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(gvar, bs.bn);
+  GPK_O_ADD(wsdA, bs.ws);
+  GPK_O_ADD(wsK, bs.ws);
+  GPK_O_ADD(wspart, bs.ws);
+  GPK_O_ADD(dX, bs.bn * D);
   using G = VarGeo<MB>;
   constexpr int TW = G::TW, MP = G::MP, QST = G::QST;
   constexpr int Dq = DQ, ds = DQ + 2, NDT = DQ / 16;
@@ -1246,7 +1277,14 @@ gpk_var_adja_l_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                       const float* __restrict__ vstd, const float* __restrict__ hyp,
                       const float* __restrict__ gmean, const float* __restrict__ gvar, int N, int M,
                       int D, int nchunks, long long BN, float* __restrict__ wsdA,
-                      float* __restrict__ wsK, float* __restrict__ wspart) {
+                      float* __restrict__ wsK, float* __restrict__ wspart, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(gvar, bs.bn);
+  GPK_O_ADD(wsdA, bs.ws);
+  GPK_O_ADD(wsK, bs.ws);
+  GPK_O_ADD(wspart, bs.ws);
   using G = LAdjGeo<MB, DQ>;
   constexpr int NWV = G::NWV, NT = G::NT, DS = G::DS, NPASS = G::NPASS, DV = G::DV;
   extern __shared__ __attribute__((aligned(16))) float vsm[];
@@ -1442,7 +1480,14 @@ gpk_var_adjk_l_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                       const float* __restrict__ vstd, const float* __restrict__ hyp,
                       const float* __restrict__ gmean, int N, int M, int D, int nchunks,
                       long long BN, const float* __restrict__ wsdA, const float* __restrict__ wsK,
-                      float* __restrict__ wspart, float* __restrict__ dX) {
+                      float* __restrict__ wspart, float* __restrict__ dX, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(wsdA, bs.ws);
+  GPK_O_ADD(wsK, bs.ws);
+  GPK_O_ADD(wspart, bs.ws);
+  GPK_O_ADD(dX, bs.bn * D);
   using G = LAdjGeo<MB, DQ>;
   constexpr int NWV = G::NWV, NT = G::NT, DS = G::DS, NPASS = G::NPASS, DV = G::DV, NDT = G::NDT;
   constexpr int NLD = G::MP * LTW / NT;   // workspace elements per thread per array
@@ -1744,7 +1789,12 @@ gpk_var_kgram_l_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                        const float* __restrict__ vmean, const float* __restrict__ vstd,
                        const float* __restrict__ hyp, const float* __restrict__ gmean,
                        const float* __restrict__ gvar, const float* __restrict__ saved, int N, int M,
-                       int D, int nchunks, float* __restrict__ gpart) {
+                       int D, int nchunks, float* __restrict__ gpart, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(gvar, bs.bn);
+  GPK_O_ADD(saved, bs.sv);
+  GPK_O_ADD(gpart, bs.ws);
   using G = LGramGeo<MB, DQ>;
   using SV = LSaved<MB>;
   constexpr int NT = G::NT, DS = G::DS, NPASS = G::NPASS, DV = G::DV, KS = G::KS;
@@ -1980,7 +2030,16 @@ gpk_var_adjs_l_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                       const float* __restrict__ vstd, const float* __restrict__ hyp,
                       const float* __restrict__ gmean, const float* __restrict__ gvar,
                       const float* __restrict__ saved, int N, int M, int D, int nchunks,
-                      float* __restrict__ wspart, float* __restrict__ dX, float* __restrict__ cm_out) {
+                      float* __restrict__ wspart, float* __restrict__ dX, float* __restrict__ cm_out,
+                      GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(gvar, bs.bn);
+  GPK_O_ADD(saved, bs.sv);
+  GPK_O_ADD(wspart, bs.ws);
+  GPK_O_ADD(dX, bs.bn * D);
+  GPK_O_ADD(cm_out, bs.ws);
   using G = LAdjGeo<MB, DQ>;
   using SV = LSaved<MB>;
   constexpr int NWV = G::NWV, NT = G::NT, DS = G::DS, NPASS = G::NPASS, DV = G::DV, NDT = G::NDT;
@@ -2313,7 +2372,10 @@ constexpr int DLST = 34;   // LDS row stride (floats): 2c + g spreads the MFMA o
 
 __global__ void __launch_bounds__(256)
 gpk_dlinv_kernel(const float* __restrict__ dA, const float* __restrict__ Kz, int M, long long BN,
-                 int ntiles, long long cols_per_split, double* __restrict__ part) {
+                 int ntiles, long long cols_per_split, double* __restrict__ part, GpkOStr bs) {
+  GPK_O_ADD(dA, bs.ws);
+  GPK_O_ADD(Kz, bs.ws);
+  GPK_O_ADD(part, bs.ws / 2);
   __shared__ float sa[64 * DLST];
   __shared__ float sb[64 * DLST];
   const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
@@ -2406,7 +2468,13 @@ __global__ void __launch_bounds__(256)
 gpk_var_red_kernel(const float* __restrict__ wspart, int nwg, int P, double* __restrict__ tot,
                    const double* __restrict__ dlpart, int nsplit, int ntiles, int M,
                    double* __restrict__ dLinv, const float* __restrict__ wspart2, int P2,
-                   double* __restrict__ tot2) {
+                   double* __restrict__ tot2, GpkOStr bs) {
+  GPK_O_ADD(wspart, bs.ws);
+  GPK_O_ADD(tot, bs.ws / 2);
+  GPK_O_OPT(dlpart, bs.ws / 2);
+  GPK_O_OPT(dLinv, M * M);
+  GPK_O_OPT(wspart2, bs.ws);
+  GPK_O_OPT(tot2, bs.ws / 2);
   __shared__ double red[8][33];
   const int tid = threadIdx.x, o = tid & 31, q0 = tid >> 5;
   const int nblk_a = (P + 31) / 32;
@@ -2490,7 +2558,21 @@ __global__ void __launch_bounds__(256)
 gpk_var_fin_kernel(const float* __restrict__ Z, const float* __restrict__ vstd,
                    const float* __restrict__ hyp, const double* __restrict__ tot, int M, int D,
                    float* __restrict__ dZ, float* __restrict__ dpar, const float* __restrict__ cm_in,
-                   VarGdlArgs gd) {
+                   VarGdlArgs gd, GpkOStr bs) {
+  GPK_O_ADD(Z, M * D);
+  GPK_O_ADD(vstd, M);
+  GPK_O_ADD(hyp, 4 + 2 * D);
+  GPK_O_ADD(tot, bs.ws / 2);
+  GPK_O_ADD(dZ, M * D);
+  GPK_O_ADD(dpar, 2 * M + 2 * D + 2);
+  GPK_O_OPT(cm_in, bs.ws);
+  if (gd.gtot != nullptr) {
+    GPK_O_ADD(gd.gtot, bs.ws / 2);
+    GPK_O_ADD(gd.Linv, M * M);
+    GPK_O_ADD(gd.vmean, M);
+    GPK_O_ADD(gd.vstd, M);
+    GPK_O_ADD(gd.dLinv, M * M);
+  }
   extern __shared__ __attribute__((aligned(16))) float fzs[];   // M x D zs (centred Z / l)
   __shared__ double red[256];
   __shared__ float cmf[64];
@@ -2624,9 +2706,8 @@ gpk_var_fin_kernel(const float* __restrict__ Z, const float* __restrict__ vstd,
 }
 
 // the two output launches (ws: nblk x D doubles of dl partials, then D floats of the centre)
-int launch_var_fin(const float* Z, const float* vstd, const float* hyp, const double* tot, int M, int D,
-                   float* dZ, float* dpar, hipStream_t stream, const float* cm_in = nullptr,
-                   const VarGdlArgs* gd = nullptr);
+int launch_var_fin(const GpkVarAdjArgs& a, const double* tot, GpkOStr bs, hipStream_t stream,
+                   const float* cm_in = nullptr, const VarGdlArgs* gd = nullptr);
 
 // ---------------------------------------------------------------------------
 // Register-resident variants for M <= 64, D <= 32 (BASELINE cfg 5: M = 64, D = 32).
@@ -2819,7 +2900,11 @@ gpk_var_fwd_r_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                      const double* __restrict__ Linv, const float* __restrict__ vmean,
                      const float* __restrict__ vstd, const float* __restrict__ hyp, int B, int N,
                      int M, int D, float* __restrict__ mean_out, float* __restrict__ var_out,
-                     int* __restrict__ flags) {
+                     int* __restrict__ flags, GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(mean_out, bs.bn);
+  GPK_O_ADD(var_out, bs.bn);
   using L = RegLds<DQ>;
   extern __shared__ __attribute__((aligned(16))) float vsm[];
   const float s2 = hyp[0], jit = hyp[2], b0 = hyp[3];
@@ -2903,7 +2988,16 @@ gpk_var_adj_r_kernel(const float* __restrict__ X, const float* __restrict__ Z,
                      const float* __restrict__ vstd, const float* __restrict__ hyp,
                      const float* __restrict__ gmean, const float* __restrict__ gvar, int B, int N,
                      int M, int D, long long BN, float* __restrict__ wsgv,
-                     float* __restrict__ wspart, float* __restrict__ cm_out, float* __restrict__ dX) {
+                     float* __restrict__ wspart, float* __restrict__ cm_out, float* __restrict__ dX,
+                     GpkOStr bs) {
+  GPK_O_MODEL();
+  GPK_O_ADD(Linv, M * M);
+  GPK_O_ADD(gmean, bs.bn);
+  GPK_O_ADD(gvar, bs.bn);
+  GPK_O_ADD(wsgv, bs.ws);
+  GPK_O_ADD(wspart, bs.ws);
+  GPK_O_ADD(cm_out, bs.ws);
+  GPK_O_ADD(dX, bs.bn * D);
   using L = RegLds<DQ, NW, FG>;
   constexpr int NDT = DQ / 16;
   extern __shared__ __attribute__((aligned(16))) float vsm[];
@@ -3425,6 +3519,16 @@ int chunk_grid(long long nchunks, int per_cu) {
   return (int)(nchunks < cap ? nchunks : cap);
 }
 
+// Per-output strides of a launch (GpkOStr): the forward's, and the adjoint's over workspace
+// slices of ws_bytes (a plan's total, a multiple of 256) each.
+GpkOStr fwd_strides(const GpkVarArgs& a) {
+  return {a.x_stride, (long long)a.B * a.N, (long long)(gpk_var_saved_bytes(a.B, a.N, a.M, a.D) / sizeof(float)), 0};
+}
+GpkOStr adj_strides(const GpkVarAdjArgs& a, size_t ws_bytes) {
+  return {a.x_stride, (long long)a.B * a.N, (long long)(gpk_var_saved_bytes(a.B, a.N, a.M, a.D) / sizeof(float)),
+          (long long)(ws_bytes / sizeof(float))};
+}
+
 template <int MB>
 int launch_var_fwd(const GpkVarArgs& a, int* flags, hipStream_t stream) {
   using G = VarGeo<MB>;
@@ -3433,9 +3537,9 @@ int launch_var_fwd(const GpkVarArgs& a, int* flags, hipStream_t stream) {
   set_lds_once<gpk_var_fwd_kernel<MB>>();
   const long long nch = (long long)a.B * ((a.N + G::TW - 1) / G::TW);
   if (nch > 0x7fffffffLL) return -8;
-  hipLaunchKernelGGL((gpk_var_fwd_kernel<MB>), dim3(chunk_grid(nch, 4)), dim3(256), lds, stream,
+  hipLaunchKernelGGL((gpk_var_fwd_kernel<MB>), dim3(chunk_grid(nch, 4), a.O), dim3(256), lds, stream,
                      a.X, a.Z, a.Linv, a.vmean, a.vstd, a.hyp, a.N, a.M, a.D, (int)nch, a.mean,
-                     a.var, flags);
+                     a.var, flags, fwd_strides(a));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   if (a.ell != nullptr) {
@@ -3472,9 +3576,9 @@ int launch_var_fwd_l(const GpkVarArgs& a, int* flags, hipStream_t stream) {
   const int per_cu = G::NWV <= 4 ? 2 : 1;   // <= 2 waves per SIMD (256 VGPRs: L^{-1} resident)
   // the training forward keeps A for the adjoint when the saved-state adjoint serves this shape
   float* saved = (a.saved != nullptr && var_saved_path<MB, DQ>(a.M)) ? a.saved : nullptr;
-  hipLaunchKernelGGL((gpk_var_fwd_l_kernel<MB, DQ>), dim3(chunk_grid(nch, per_cu)), dim3(G::NT), lds,
+  hipLaunchKernelGGL((gpk_var_fwd_l_kernel<MB, DQ>), dim3(chunk_grid(nch, per_cu), a.O), dim3(G::NT), lds,
                      stream, a.X, a.Z, a.Linv, a.vmean, a.vstd, a.hyp, a.N, a.M, a.D, (int)nch,
-                     a.mean, a.var, flags, saved);
+                     a.mean, a.var, flags, saved, fwd_strides(a));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   if (a.ell != nullptr) {
@@ -3578,8 +3682,8 @@ int launch_var_fwd_r(const GpkVarArgs& a, int* flags, hipStream_t stream) {
   set_lds_once<gpk_var_fwd_r_kernel<DQ>>();
   const long long nch = (long long)a.B * ((a.N + 31) / 32);
   const long long nwg = (nch + 3) / 4 < 768 ? (nch + 3) / 4 : 768;
-  hipLaunchKernelGGL((gpk_var_fwd_r_kernel<DQ>), dim3((unsigned)nwg), dim3(256), lds, stream, a.X, a.Z,
-                     a.Linv, a.vmean, a.vstd, a.hyp, a.B, a.N, a.M, a.D, a.mean, a.var, flags);
+  hipLaunchKernelGGL((gpk_var_fwd_r_kernel<DQ>), dim3((unsigned)nwg, a.O), dim3(256), lds, stream, a.X, a.Z,
+                     a.Linv, a.vmean, a.vstd, a.hyp, a.B, a.N, a.M, a.D, a.mean, a.var, flags, fwd_strides(a));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   if (a.ell != nullptr) {
@@ -3602,6 +3706,7 @@ int launch_var_adj(const GpkVarAdjArgs& a, hipStream_t stream) {
     return launch_var_adj_saved<MB, DQ>(a, stream);
   }
   const AdjPlan p = adj_plan<MB>(a.B, a.N, a.M, a.D);
+  const GpkOStr bs = adj_strides(a, p.total);   // output o works in workspace slice o
   char* ws = (char*)a.ws;
   float* wsdA = (float*)(ws + p.off_dA);
   float* wsK = (float*)(ws + p.off_K);
@@ -3616,34 +3721,34 @@ int launch_var_adj(const GpkVarAdjArgs& a, hipStream_t stream) {
     static_assert(RegLds<RQ, NW, FG>::adj_total * sizeof(float) <= 160 * 1024, "LDS per workgroup");
     const size_t lds = (size_t)RegLds<RQ, NW, FG>::adj_total * sizeof(float);
     set_lds_once<gpk_var_adj_r_kernel<RQ, NW, FG>>();
-    hipLaunchKernelGGL((gpk_var_adj_r_kernel<RQ, NW, FG>), dim3(p.nwg), dim3(64 * NW), lds, stream, a.X,
+    hipLaunchKernelGGL((gpk_var_adj_r_kernel<RQ, NW, FG>), dim3(p.nwg, a.O), dim3(64 * NW), lds, stream, a.X,
                        a.Z, a.Linv, a.vmean, a.vstd, a.hyp, a.gmean, a.gvar, a.B, a.N, a.M, a.D, p.BN,
-                       wsgv, wspart, wsgv, a.dX);
+                       wsgv, wspart, wsgv, a.dX, bs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     // one fixed-order reduction of the [adjoint | K-Gram] rows; dL^{-1} in the output launch
     const int PR = p.P + kGPart;
-    hipLaunchKernelGGL(gpk_var_red_kernel, dim3((PR + 31) / 32), dim3(256), 0, stream, wspart, p.nwg, PR,
-                       tot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr);
+    hipLaunchKernelGGL(gpk_var_red_kernel, dim3((PR + 31) / 32, a.O), dim3(256), 0, stream, wspart, p.nwg, PR,
+                       tot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr, bs);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     const VarGdlArgs gd{gtot, a.Linv, a.vmean, a.vstd, a.dLinv, 0};
-    return launch_var_fin(a.Z, a.vstd, a.hyp, tot, a.M, a.D, a.dZ, a.dpar, stream, wsgv, &gd);
+    return launch_var_fin(a, tot, bs, stream, wsgv, &gd);
   }
   if constexpr (var_adj_lreg_fits<MB, DQ>()) {
     if (GPK_VAR_LREG && a.M > 64 && (long long)a.M * p.BN * 4 < (1LL << 31)) {
       using LG = LAdjGeo<MB, DQ>;
       set_lds_once<gpk_var_adja_l_kernel<MB, DQ>>();
       set_lds_once<gpk_var_adjk_l_kernel<MB, DQ>>();
-      hipLaunchKernelGGL((gpk_var_adja_l_kernel<MB, DQ>), dim3(p.nwg), dim3(LG::NT),
+      hipLaunchKernelGGL((gpk_var_adja_l_kernel<MB, DQ>), dim3(p.nwg, a.O), dim3(LG::NT),
                          (size_t)LG::a_total * sizeof(float), stream, a.X, a.Z, a.Linv, a.vmean,
                          a.vstd, a.hyp, a.gmean, a.gvar, a.N, a.M, a.D, p.nchunks, p.BN, wsdA, wsK,
-                         wspart);
+                         wspart, bs);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL((gpk_var_adjk_l_kernel<MB, DQ>), dim3(p.nwg), dim3(LG::NT),
+      hipLaunchKernelGGL((gpk_var_adjk_l_kernel<MB, DQ>), dim3(p.nwg, a.O), dim3(LG::NT),
                          (size_t)LG::k_total * sizeof(float), stream, a.X, a.Z, a.Linv, a.vmean,
                          a.vstd, a.hyp, a.gmean, a.N, a.M, a.D, p.nchunks, p.BN, wsdA, wsK, wspart,
-                         a.dX);
+                         a.dX, bs);
       e = hipGetLastError();
       if (e != hipSuccess) return (int)e;
       return launch_var_adj_tail(a, p, stream);
@@ -3652,17 +3757,17 @@ int launch_var_adj(const GpkVarAdjArgs& a, hipStream_t stream) {
   const size_t lds = var_adj_lds<MB, DQ>();
   if (lds > 160 * 1024) return -12;
   set_lds_once<gpk_var_adj_kernel<MB, DQ>>();
-  hipLaunchKernelGGL((gpk_var_adj_kernel<MB, DQ>), dim3(p.nwg), dim3(256), lds, stream, a.X, a.Z,
+  hipLaunchKernelGGL((gpk_var_adj_kernel<MB, DQ>), dim3(p.nwg, a.O), dim3(256), lds, stream, a.X, a.Z,
                      a.Linv, a.vmean, a.vstd, a.hyp, a.gmean, a.gvar, a.N, a.M, a.D, p.nchunks,
-                     p.BN, wsdA, wsK, wspart, a.dX);
+                     p.BN, wsdA, wsK, wspart, a.dX, bs);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   return launch_var_adj_tail(a, p, stream);
 }
 
-int launch_var_fin(const float* Z, const float* vstd, const float* hyp, const double* tot, int M, int D,
-                   float* dZ, float* dpar, hipStream_t stream, const float* cm_in,
-                   const VarGdlArgs* gd) {
+int launch_var_fin(const GpkVarAdjArgs& a, const double* tot, GpkOStr bs, hipStream_t stream,
+                   const float* cm_in, const VarGdlArgs* gd) {
+  const int M = a.M, D = a.D;
   const int nblk = (M + kFinRows - 1) / kFinRows;
   set_lds_once<gpk_var_fin_kernel, 64 * 1024>();   // + ~3.3 KB static
   size_t lds = (size_t)M * D * sizeof(float);
@@ -3678,8 +3783,8 @@ int launch_var_fin(const float* Z, const float* vstd, const float* hyp, const do
       ngd = (int)(((long long)M * M + 255) / 256);
     }
   }
-  hipLaunchKernelGGL(gpk_var_fin_kernel, dim3(nblk + 1 + ngd), dim3(256), lds, stream, Z,
-                     vstd, hyp, tot, M, D, dZ, dpar, cm_in, g);
+  hipLaunchKernelGGL(gpk_var_fin_kernel, dim3(nblk + 1 + ngd, a.O), dim3(256), lds, stream, a.Z,
+                     a.vstd, a.hyp, tot, M, D, a.dZ, a.dpar, cm_in, g, bs);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }
@@ -3692,16 +3797,17 @@ int launch_var_adj_tail(const GpkVarAdjArgs& a, const AdjPlan& p, hipStream_t st
   float* wspart = (float*)(ws + p.off_part);
   double* tot = (double*)(ws + p.off_tot);
   double* dl = (double*)(ws + p.off_dl);
-  hipLaunchKernelGGL(gpk_dlinv_kernel, dim3(p.ntiles * p.nsplit), dim3(256), 0, stream, wsdA, wsK,
-                     a.M, p.BN, p.ntiles, p.cols_per_split, dl);
+  const GpkOStr bs = adj_strides(a, p.total);
+  hipLaunchKernelGGL(gpk_dlinv_kernel, dim3(p.ntiles * p.nsplit, a.O), dim3(256), 0, stream, wsdA, wsK,
+                     a.M, p.BN, p.ntiles, p.cols_per_split, dl, bs);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
   const long long nred = (p.P + 31) / 32 + ((long long)a.M * a.M + 31) / 32;
-  hipLaunchKernelGGL(gpk_var_red_kernel, dim3((unsigned)nred), dim3(256), 0, stream,
-                     wspart, p.nwg, p.P, tot, dl, p.nsplit, p.ntiles, a.M, a.dLinv, nullptr, 0, nullptr);
+  hipLaunchKernelGGL(gpk_var_red_kernel, dim3((unsigned)nred, a.O), dim3(256), 0, stream,
+                     wspart, p.nwg, p.P, tot, dl, p.nsplit, p.ntiles, a.M, a.dLinv, nullptr, 0, nullptr, bs);
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  return launch_var_fin(a.Z, a.vstd, a.hyp, tot, a.M, a.D, a.dZ, a.dpar, stream);
+  return launch_var_fin(a, tot, bs, stream);
 }
 
 // ---- the saved-state adjoint (M > 64): workspace G' partials | adjoint partials | their fp64 totals
@@ -3741,39 +3847,39 @@ int launch_var_adj_saved(const GpkVarAdjArgs& a, hipStream_t stream) {
     using LA = LAdjGeo<MB, DQ>;
     using LG = LGramGeo<MB, DQ>;
     const AdjSavedPlan p = adj_saved_plan<MB, DQ>(a.B, a.N, a.M, a.D);
+    const GpkOStr bs = adj_strides(a, p.total);   // output o works in workspace slice o
     char* ws = (char*)a.ws;
     float* gpart = (float*)(ws + p.off_gpart);
     float* wspart = (float*)(ws + p.off_part);
     double* tot = (double*)(ws + p.off_tot);
     double* gtot = (double*)(ws + p.off_gtot);
     set_lds_once<gpk_var_adjs_l_kernel<MB, DQ>>();
-    hipLaunchKernelGGL((gpk_var_adjs_l_kernel<MB, DQ>), dim3(p.nwg), dim3(LA::NT), (size_t)LA::k_total * sizeof(float),
+    hipLaunchKernelGGL((gpk_var_adjs_l_kernel<MB, DQ>), dim3(p.nwg, a.O), dim3(LA::NT), (size_t)LA::k_total * sizeof(float),
                        stream, a.X, a.Z, a.Linv, a.vmean, a.vstd, a.hyp, a.gmean, a.gvar, a.saved, a.N, a.M,
-                       a.D, p.nchunks, wspart, a.dX, (float*)(ws + p.off_cm));
+                       a.D, p.nchunks, wspart, a.dX, (float*)(ws + p.off_cm), bs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     set_lds_once<gpk_var_kgram_l_kernel<MB, DQ>>();
-    hipLaunchKernelGGL((gpk_var_kgram_l_kernel<MB, DQ>), dim3(p.nwg_g), dim3(LG::NT), (size_t)LG::total * sizeof(float),
+    hipLaunchKernelGGL((gpk_var_kgram_l_kernel<MB, DQ>), dim3(p.nwg_g, a.O), dim3(LG::NT), (size_t)LG::total * sizeof(float),
                        stream, a.X, a.Z, a.vmean, a.vstd, a.hyp, a.gmean, a.gvar, a.saved, a.N, a.M, a.D,
-                       p.nchunks, gpart);
+                       p.nchunks, gpart, bs);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     // one fixed-order reduction launch for both partial arrays (same workgroup count), then
     // the output launch with dL^{-1} in extra workgroups
     if (p.nwg == p.nwg_g) {
-      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.P + 31) / 32 + (p.PG + 31) / 32), dim3(256), 0, stream,
-                         wspart, p.nwg, p.P, tot, nullptr, 0, 0, 0, nullptr, gpart, p.PG, gtot);
+      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.P + 31) / 32 + (p.PG + 31) / 32, a.O), dim3(256), 0, stream,
+                         wspart, p.nwg, p.P, tot, nullptr, 0, 0, 0, nullptr, gpart, p.PG, gtot, bs);
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     } else {
-      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.PG + 31) / 32), dim3(256), 0, stream, gpart, p.nwg_g,
-                         p.PG, gtot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr);
+      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.PG + 31) / 32, a.O), dim3(256), 0, stream, gpart, p.nwg_g,
+                         p.PG, gtot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr, bs);
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.P + 31) / 32), dim3(256), 0, stream, wspart, p.nwg, p.P,
-                         tot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr);
+      hipLaunchKernelGGL(gpk_var_red_kernel, dim3((p.P + 31) / 32, a.O), dim3(256), 0, stream, wspart, p.nwg, p.P,
+                         tot, nullptr, 0, 0, 0, nullptr, nullptr, 0, nullptr, bs);
       if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     }
     const VarGdlArgs gd{gtot, a.Linv, a.vmean, a.vstd, a.dLinv, MB};
-    return launch_var_fin(a.Z, a.vstd, a.hyp, tot, a.M, a.D, a.dZ, a.dpar, stream,
-                          (const float*)(ws + p.off_cm), &gd);
+    return launch_var_fin(a, tot, bs, stream, (const float*)(ws + p.off_cm), &gd);
   } else {
     return -13;
   }

@@ -545,23 +545,6 @@ class MeanFieldVariationalDistribution(nn.Module):
         return 0.5 * (s2.sum(-1) + m.pow(2).sum(-1) - m.shape[-1] - s2.log().sum(-1))
 
 
-class _MeanOutput:
-    """Output o's view of a layer mean (DeepGP.py:42-45): ConstantMean(batch_shape=[O]) has one
-    constant per output, the reference's LinearMean(input_dims) one weight vector for all."""
-
-    def __init__(self, mean_module, o):
-        if hasattr(mean_module, "weights"):
-            w = mean_module.weights
-            self.weights = w[o] if w.dim() == 3 else w
-            b = mean_module.bias
-            self.bias = (b[o] if b.dim() == 2 else b) if b is not None else None
-        elif hasattr(mean_module, "constant"):
-            c = mean_module.constant
-            self.constant = c[o] if c.dim() == 2 else c
-        else:
-            raise NotImplementedError(f"mean module {type(mean_module).__name__}")
-
-
 def variational_dense_covariance(x, Z, Linv, vstd, outputscale, lengthscale, jitter):
     """The full predictive covariance of q(f) at x (B', N, D), as upstream
     VariationalStrategy.forward (whitened) builds it lazily: K_XX + jitter I + A^T (S - I) A with
@@ -606,20 +589,15 @@ class VariationalStrategy(nn.Module):
         self.jitter_val = jitter_val
         self._initialized = False     # host mirror of the buffer: no device sync per call
         from .ops_autograd import KzzCache
-        self._kzz_cache = KzzCache()
-        self._kzz_caches = []            # multi-output layers: one cache per output
+        self._kzz_cache = KzzCache()     # multi-output layers: the (O, M, M) factor is one entry
 
     def _load_from_state_dict(self, *args, **kwargs):
         super()._load_from_state_dict(*args, **kwargs)
         self._initialized = bool(int(self.variational_params_initialized))
         self._kzz_cache.clear()
-        for c in self._kzz_caches:
-            c.clear()
 
     def train(self, mode: bool = True):
         self._kzz_cache.clear()      # GPyTorch clears its cholesky cache on mode switches
-        for c in self._kzz_caches:
-            c.clear()
         return super().train(mode)
 
     @property
@@ -668,8 +646,12 @@ class VariationalStrategy(nn.Module):
     def _call_batched(self, x: torch.Tensor) -> MultivariateNormal:
         """Multi-output layer (output_dims = O, DeepGP.py:24-26): inducing points (O, M, D), q(u)
         batch (O,), kernel hyper-parameters per output; x (..., O, N, D) as DeepGPLayer.__call__
-        expands it. The O outputs are independent GPs: one K_ZZ factor (cached per output) and
-        one variational launch each. Returns the batch (..., O) of per-output q(f)."""
+        expands it. The O outputs are independent GPs on ONE launch chain each way
+        (ops_autograd.variational_predict_batched): the O K_ZZ factors are one cache entry, the
+        expanded inputs are read in place by every output (no (O, B, N, D) copy), and the
+        per-output dLinv flow into one batched K_ZZ adjoint. Returns the batch (..., O) of
+        per-output q(f); the covariance stays dense torch arithmetic from Linv[o] on request."""
+        from .ops_autograd import variational_predict_batched
         Z = self.inducing_points
         O, M, D = Z.shape
         if x.dim() < 3 or x.shape[-3] != O:
@@ -679,30 +661,26 @@ class VariationalStrategy(nn.Module):
         model = self.model
         kern = model.covar_module
         q = self._variational_distribution
-        if len(self._kzz_caches) != O:
-            from .ops_autograd import KzzCache
-            self._kzz_caches = [KzzCache() for _ in range(O)]
         key = (Z, kern.raw_outputscale, kern.base_kernel.raw_lengthscale)
         s2 = kern.outputscale.reshape(O)
         ls = kern.base_kernel.lengthscale.reshape(O, -1)
         vm = q.variational_mean.reshape(O, M)
         vs = q._variational_stddev.reshape(O, M)
-        means, variances, flags, covs = [], [], [], []
-        for o in range(O):
-            xo = x[..., o, :, :].reshape(-1, N, D)
-            m, v, f, c = self._predict_one(xo, Z[o], vm[o], vs[o], s2[o], ls[o], _MeanOutput(model.mean_module, o),
-                                           self._jitter(x.dtype), self._kzz_caches[o], key)
-            means.append(m.reshape(*batch, N))
-            variances.append(v.reshape(*batch, N))
-            flags.append(f)
-            covs.append(c)
-        flag = flags[0]
-        for f in flags[1:]:
-            flag = torch.bitwise_or(flag, f)
+        jitter = self._jitter(x.dtype)
+        if x.stride(-3) == 0 or O == 1:     # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
+            xk = x[..., 0, :, :].reshape(-1, N, D)
+        else:
+            xk = x.movedim(-3, 0).reshape(O, -1, N, D)
+        mean, var, flag, Linv = variational_predict_batched(
+            xk, Z, vm, vs, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
+            return_linv=True)
 
         def cov():
-            return torch.stack([c().reshape(*batch, N, N) for c in covs], dim=-3)
-        return MultivariateNormal(torch.stack(means, dim=-2), torch.stack(variances, dim=-2), clamp_flag=flag,
+            xo = xk.expand(O, *xk.shape) if xk.dim() == 3 else xk
+            return torch.stack([variational_dense_covariance(xo[o], Z[o], Linv[o], vs[o], s2[o], ls[o], jitter)
+                                .reshape(*batch, N, N) for o in range(O)], dim=-3)
+        return MultivariateNormal(mean.reshape(O, *batch, N).movedim(0, -2).contiguous(),
+                                  var.reshape(O, *batch, N).movedim(0, -2).contiguous(), clamp_flag=flag,
                                   covar_fn=cov)
 
 

@@ -13,6 +13,9 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter) -> (mean, var, flags, hyper)
                                                                                [autograd]
   gpk::variational_adj(x, Linv, Z, vmean, vstd, hyper, gmean, gvar) -> (dX, dLinv, dZ, dpar)
+  gpk::kzz_factor_batched / gpk::variational_fwd_batched / gpk::variational_adj_batched
+      the three ops above for the O output GPs of a multi-output layer (leading O on every
+      array, the inputs shared or per output), one launch chain for all outputs    [autograd]
   gpk::gauss_ell(y, mean, var, noise) -> ell (R,)                             [autograd]
   gpk::meanfield_kl(m, s) -> kl (1,)                                          [autograd]
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
@@ -223,11 +226,148 @@ def _var_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
 variational_fwd.register_autograd(_var_backward, setup_context=_var_setup)
 
 # ---------------------------------------------------------------------------
+# multi-output layers (output_dims = O): the same chain with an output dimension, ONE launch
+# of every kernel for all outputs (gpk_kzz_chol_f64_batched / gpk_variational_batched_f32 /
+# gpk_variational_adjoint_batched_f32 / gpk_kzz_backward_f64_batched)
+# ---------------------------------------------------------------------------
+
+
+def _kzz_hyper_batched(Z, s2, ls):
+    O, _, D = Z.shape
+    return torch.cat([s2.detach().reshape(O, 1).float(), ls.detach().reshape(O, -1).expand(O, D).float()], dim=1)
+
+
+@torch.library.custom_op("gpk::kzz_factor_batched", mutates_args=(), device_types="cuda")
+def kzz_factor_batched(Z: Tensor, s2: Tensor, ls: Tensor, jitter: float, chol_jitter: float,
+                       max_tries: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Z (O, M, D), s2 (O,), ls (O, D) or (O, 1) -> (Linv, L (O, M, M) float64, info (O,))."""
+    kz = ops.kzz_cholesky_batched(Z.detach(), _kzz_hyper_batched(Z, s2, ls), jitter=jitter,
+                                  chol_jitter=chol_jitter, max_tries=max_tries)
+    return kz.Linv, kz.L, kz.info
+
+
+@kzz_factor_batched.register_fake
+def _(Z, s2, ls, jitter, chol_jitter, max_tries):
+    O, M, _ = Z.shape
+    return (Z.new_empty(O, M, M, dtype=torch.float64), Z.new_empty(O, M, M, dtype=torch.float64),
+            Z.new_empty(O, dtype=torch.int32))
+
+
+def _kzzb_setup(ctx, inputs, output):
+    Z, s2, ls = inputs[:3]
+    Linv, L, info = output
+    ctx.save_for_backward(Z, s2, ls, L, Linv)
+    ctx.mark_non_differentiable(L, info)
+
+
+def _kzzb_backward(ctx, dLinv, _dL, _dinfo):
+    """The per-output dLinv of every call that shared the factors -> one batched K_ZZ adjoint."""
+    Z, s2, ls, L, Linv = ctx.saved_tensors
+    if dLinv is None:
+        return None, None, None, None, None, None
+    O, _, D = Z.shape
+    dZ, dhyp = ops.kzz_backward_batched(dLinv, L, Linv, Z, _kzz_hyper_batched(Z, s2, ls))
+    dls = dhyp[:, 1:]
+    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
+    return (dZ.to(Z.dtype), dhyp[:, 0].reshape(s2.shape).to(s2.dtype), dls.to(ls.dtype), None, None, None)
+
+
+kzz_factor_batched.register_autograd(_kzzb_backward, setup_context=_kzzb_setup)
+
+
+def _var_hyper_batched(x, O, s2, ls, w, b0, jitter):
+    """(O, 4 + 2D) rows {s2, noise = 1, jitter, b0, w[D], ls[D]}; a mean shared by all outputs
+    (w (D,), b0 one value) is repeated."""
+    D = x.shape[-1]
+    one = x.new_ones(O, 1)
+    return torch.cat([s2.detach().reshape(O, 1).float(), one, one * float(jitter),
+                      b0.detach().reshape(-1, 1).expand(O, 1).float(), w.detach().reshape(-1, D).expand(O, D).float(),
+                      ls.detach().reshape(O, -1).expand(O, D).float()], dim=1)
+
+
+def _saved_numel_batched(x, Z, save):
+    if not save:
+        return 0
+    B, N, D = x.shape[-3:]
+    return Z.shape[0] * (_native.lib().gpk_variational_saved_bytes(B, N, Z.shape[1], D) // 4)
+
+
+@torch.library.custom_op("gpk::variational_fwd_batched", mutates_args=(), device_types="cuda")
+def variational_fwd_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, s2: Tensor,
+                            ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
+                            save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """x (B, N, D) shared by the O outputs, or (O, B, N, D); Linv (O, M, M), Z (O, M, D),
+    vmean / vstd (O, M), s2 (O,), ls (O, D) or (O, 1); the mean per output (w (O, D), b0 (O,))
+    or shared (w (D,), b0 one value) -> (mean, var (O, B, N), clamp flags (1,), packed hyper
+    (O, 4 + 2D), saved state), as gpk::variational_fwd."""
+    hyper = _var_hyper_batched(x, Z.shape[0], s2, ls, w, b0, jitter)
+    out = ops.variational_forward_batched(x, Z, Linv, vmean, vstd, hyper, save=save)
+    saved = out.saved if out.saved is not None else x.new_empty(0)
+    return out.mean, out.var, out.flags, hyper, saved
+
+
+@variational_fwd_batched.register_fake
+def _(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter, save=False):
+    B, N, D = x.shape[-3:]
+    O = Z.shape[0]
+    return (x.new_empty(O, B, N), x.new_empty(O, B, N), x.new_empty(1, dtype=torch.int32),
+            x.new_empty(O, 4 + 2 * D), x.new_empty(_saved_numel_batched(x, Z, save)))
+
+
+@torch.library.custom_op("gpk::variational_adj_batched", mutates_args=(), device_types="cuda")
+def variational_adj_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, hyper: Tensor,
+                            gmean: Tensor, gvar: Tensor,
+                            saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX (O, B, N, D) per output, dLinv (O, M, M), dZ (O, M, D), dpar (O, 2M + 2D + 2))."""
+    adj = ops.variational_adjoint_batched(x, Z, Linv, vmean, vstd, hyper, gmean, gvar,
+                                          saved=saved if saved.numel() > 0 else None)
+    return adj.dX, adj.dLinv, adj.dZ, adj.dpar
+
+
+@variational_adj_batched.register_fake
+def _(x, Linv, Z, vmean, vstd, hyper, gmean, gvar, saved):
+    O, M, D = Z.shape
+    B, N = x.shape[-3], x.shape[-2]
+    return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(O, 2 * M + 2 * D + 2))
+
+
+def _varb_setup(ctx, inputs, output):
+    x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter = inputs[:10]
+    ctx.save_for_backward(x, Linv, Z, vmean, vstd, s2, ls, w, b0, output[3], output[4])
+    ctx.mark_non_differentiable(output[2], output[3], output[4])
+
+
+def _varb_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
+    x, Linv, Z, vmean, vstd, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
+    O, M, D = Z.shape
+    B, N = x.shape[-3], x.shape[-2]
+    if gmean is None:
+        gmean = x.new_zeros(O, B, N)
+    if gvar is None:
+        gvar = x.new_zeros(O, B, N)
+    dX, dLinv, dZ, dpar = torch.ops.gpk.variational_adj_batched(x, Linv, Z, vmean, vstd, hyper,
+                                                                gmean.contiguous(), gvar.contiguous(), saved)
+    if x.dim() == 3:
+        dX = dX.sum(0)                      # inputs shared by the outputs
+    dls = dpar[:, 2 * M + 1:2 * M + 1 + D]
+    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
+    dw = dpar[:, 2 * M + 1 + D:2 * M + 1 + 2 * D]
+    dw = dw.sum(0).reshape(w.shape) if w.numel() == D else dw.reshape(w.shape)   # a mean shared by the outputs
+    db0 = dpar[:, 2 * M + 1 + 2 * D]
+    db0 = db0.sum().reshape(b0.shape) if b0.numel() == 1 else db0.reshape(b0.shape)
+    return (dX, dLinv, dZ, dpar[:, :M].reshape(vmean.shape), dpar[:, M:2 * M].reshape(vstd.shape),
+            dpar[:, 2 * M].reshape(s2.shape), dls, dw, db0, None, None)
+
+
+variational_fwd_batched.register_autograd(_varb_backward, setup_context=_varb_setup)
+
+# ---------------------------------------------------------------------------
 # ELBO terms (gpk_gauss_ell_f32 / gpk_meanfield_kl_f32)
 # ---------------------------------------------------------------------------
 
 
-@torch.library.custom_op("gpk::gauss_ell", mutates_args=(), device_types="cuda")
+@torch.library.custom_op("gpk::gauss_ell",mutates_args=(), device_types="cuda")
 def gauss_ell(y: Tensor, mean: Tensor, var: Tensor, noise: Tensor) -> Tensor:
     """(R,) sums over N of GaussianLikelihood.expected_log_prob for (R, N) rows."""
     return ops.gauss_ell(y.contiguous().float(), mean.contiguous().float(), var.contiguous().float(),

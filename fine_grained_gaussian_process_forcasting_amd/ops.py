@@ -582,6 +582,179 @@ def kzz_backward(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: to
 
 
 # ---------------------------------------------------------------------------
+# Multi-output (batched) variational chain: O independent GPs in one launch of every kernel
+# (include/gpk.h::gpk_*_batched; ToyDeepGPHiddenLayer(output_dims=O), DeepGP.py:24-31)
+# ---------------------------------------------------------------------------
+def kzz_cholesky_batched(Z: torch.Tensor, hyper: torch.Tensor, jitter: float = 1e-4,
+                         chol_jitter: float = 1e-8, max_tries: int = 3) -> KzzFactor:
+    """The K_ZZ factors of O outputs (include/gpk.h::gpk_kzz_chol_f64_batched): Z (O, M, D),
+    hyper (O, 1 + D) = {outputscale, lengthscale[D]} per output -> L, Linv (O, M, M) float64
+    and info (O,), bit-identical to O ``kzz_cholesky`` calls."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    _require_device(Z, hyper)
+    Z = Z.detach().contiguous().float()
+    O, M, D = Z.shape
+    dev = Z.device
+    if tuple(hyper.shape) != (O, 1 + D):
+        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
+    hyper = hyper.detach().contiguous().float()
+    L = torch.empty(O, M, M, device=dev, dtype=torch.float64)
+    Linv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
+    info = torch.empty(O, device=dev, dtype=torch.int32)
+    rc = _native.lib().gpk_kzz_chol_f64_batched(Z.data_ptr(), hyper.data_ptr(), O, M, D, float(jitter),
+                                                float(chol_jitter), int(max_tries), L.data_ptr(),
+                                                Linv.data_ptr(), info.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_kzz_chol_f64_batched")
+    return KzzFactor(L, Linv, info)
+
+
+def kzz_backward_batched(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: torch.Tensor,
+                         hyper: torch.Tensor):
+    """``kzz_backward`` for O outputs, every launch once (gpk_kzz_backward_f64_batched):
+    dLinv, L, Linv (O, M, M) float64, Z (O, M, D), hyper (O, 1 + D) -> (dZ (O, M, D),
+    dhyp (O, 1 + D) = {ds2, dlengthscale[D]} per output)."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    for name, t in (("dLinv", dLinv), ("L", L), ("Linv", Linv)):
+        if tuple(t.shape) != (O, M, M):
+            raise ValueError(f"{name} must be (O, M, M) = {(O, M, M)}, got {tuple(t.shape)}")
+    if tuple(hyper.shape) != (O, 1 + D):
+        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
+    _require_device(dLinv, L, Linv, Z, hyper)
+    dev = Z.device
+    lib = _native.lib()
+    nbytes = lib.gpk_kzz_backward_batched_workspace_bytes(O, M, D)
+    if nbytes == 0:
+        raise ValueError(f"unsupported K_ZZ shape O={O} M={M} D={D}")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
+    dhyp = torch.empty(O, 1 + D, device=dev, dtype=torch.float32)
+    rc = lib.gpk_kzz_backward_f64_batched(
+        dLinv.detach().contiguous().double().data_ptr(), L.detach().contiguous().double().data_ptr(),
+        Linv.detach().contiguous().double().data_ptr(), Z.detach().contiguous().float().data_ptr(),
+        hyper.detach().contiguous().float().data_ptr(), O, M, D, ws.data_ptr(), dZ.data_ptr(),
+        dhyp.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_kzz_backward_f64_batched")
+    return dZ, dhyp
+
+
+def _batched_x(X: torch.Tensor, O: int):
+    """(contiguous float X, shared flag): X (B, N, D) is read by every output; an (O, B, N, D)
+    tensor whose output dimension is an expansion (stride 0) too, without a copy."""
+    if X.dim() == 3:
+        return X.detach().contiguous().float(), True
+    if X.dim() != 4 or X.shape[0] != O:
+        raise ValueError(f"X must be (B, N, D) or (O, B, N, D) with O = {O}, got {tuple(X.shape)}")
+    if O > 1 and X.stride(0) == 0:
+        return X[0].detach().contiguous().float(), True
+    return X.detach().contiguous().float(), False
+
+
+def variational_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                                vstd: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
+                                save: bool = False) -> VariationalOut:
+    """``variational_forward`` for O outputs in one launch (gpk_variational_batched_f32): X
+    (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64,
+    vmean / vstd (O, M), hyper (O, 4 + 2D) -> mean, var (O, B, N), one clamp flag word for all
+    outputs and, with ``save`` where the saved-state adjoint serves the shape, the O training
+    states in ``out.saved``. Bit-identical to O single-output calls."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    _require_device(X, Z, Linv, vmean, vstd, hyper)
+    X, shared = _batched_x(X, O)
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
+    if tuple(hyper.shape) != (O, 4 + 2 * D):
+        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+    dev = X.device
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vmean = vmean.detach().reshape(O, M).contiguous().float()
+    vstd = vstd.detach().reshape(O, M).contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    mean = torch.empty(O, B, N, device=dev, dtype=torch.float32)
+    var = torch.empty(O, B, N, device=dev, dtype=torch.float32)
+    flags = torch.empty(1, device=dev, dtype=torch.int32) if want_flags else None
+    lib = _native.lib()
+    nsaved = lib.gpk_variational_saved_bytes(B, N, M, D) if (save and B > 0) else 0
+    saved = torch.empty(O * (nsaved // 4), device=dev, dtype=torch.float32) if nsaved > 0 else None
+    rc = lib.gpk_variational_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
+        hyper.data_ptr(), O, B, N, M, D, mean.data_ptr(), var.data_ptr(),
+        flags.data_ptr() if flags is not None else None, saved.data_ptr() if saved is not None else None,
+        _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_batched_f32")
+    return VariationalOut(mean, var, None, flags, saved)
+
+
+@dataclass
+class VariationalAdjointBatched:
+    dX: torch.Tensor      # (O, B, N, D) per output (shared inputs: the caller sums over O)
+    dLinv: torch.Tensor   # (O, M, M) float64, lower
+    dZ: torch.Tensor      # (O, M, D) the K_ZX part of dZ
+    dpar: torch.Tensor    # (O, 2M + 2D + 2): dvmean (M), dvstd (M), ds2, dls (D), dw (D), db0
+
+
+def variational_adjoint_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                                vstd: torch.Tensor, hyper: torch.Tensor, gmean: torch.Tensor,
+                                gvar: torch.Tensor,
+                                saved: Optional[torch.Tensor] = None) -> VariationalAdjointBatched:
+    """``variational_adjoint`` for O outputs, every launch once
+    (gpk_variational_adjoint_batched_f32); arguments as ``variational_forward_batched`` plus
+    gmean / gvar (O, B, N) and the forward's ``saved`` state (None: recompute)."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    _require_device(X, Z, Linv, vmean, vstd, hyper, gmean, gvar)
+    X, shared = _batched_x(X, O)
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != (O, M, M):
+        raise ValueError(f"Linv must be (O, M, M) = {(O, M, M)}, got {tuple(Linv.shape)}")
+    if tuple(hyper.shape) != (O, 4 + 2 * D):
+        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+    dev = X.device
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous().double()
+    vmean = vmean.detach().reshape(O, M).contiguous().float()
+    vstd = vstd.detach().reshape(O, M).contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    gmean = gmean.detach().reshape(O, B, N).contiguous().float()
+    gvar = gvar.detach().reshape(O, B, N).contiguous().float()
+    lib = _native.lib()
+    if saved is not None:
+        # the C entry point receives a bare pointer: the dtype and device are checked here
+        if saved.dtype != torch.float32 or saved.device != dev:
+            raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device}): "
+                             f"pass variational_forward_batched(save=True).saved unchanged")
+        if saved.numel() * 4 != O * lib.gpk_variational_saved_bytes(B, N, M, D):
+            raise ValueError("saved state does not match this shape (variational_forward_batched(save=True))")
+        saved = saved.detach().contiguous()
+    nbytes = lib.gpk_variational_adjoint_batched_workspace_bytes(O, B, N, M, D, int(saved is not None))
+    if nbytes == 0:
+        raise ValueError(f"unsupported variational shape O={O} B={B} N={N} M={M} D={D}")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(O, 2 * M + 2 * D + 2, device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_adjoint_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
+        hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), saved.data_ptr() if saved is not None else None,
+        O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(),
+        _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_adjoint_batched_f32")
+    return VariationalAdjointBatched(dX, dLinv, dZ, dpar)
+
+
+# ---------------------------------------------------------------------------
 # ELBO terms (gpk_gauss_ell_f32 / gpk_meanfield_kl_f32)
 # ---------------------------------------------------------------------------
 def gauss_ell(y: torch.Tensor, mean: torch.Tensor, var: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:

@@ -79,7 +79,10 @@ class KzzCache:
         e = self._entry
         if e is not None and e["key"] == key and e["grad"] == grad and not e["spent"]:
             return e["Linv"]
-        Linv, _, info = torch.ops.gpk.kzz_factor(Z, s2, ls, float(jitter), 1e-8, 3)
+        if Z.dim() == 3:     # a multi-output layer: the O factors in one entry, one launch chain
+            Linv, _, info = torch.ops.gpk.kzz_factor_batched(Z, s2, ls, float(jitter), 1e-8, 3)
+        else:
+            Linv, _, info = torch.ops.gpk.kzz_factor(Z, s2, ls, float(jitter), 1e-8, 3)
         entry = {"key": key, "grad": grad, "Linv": Linv, "spent": False, "info": info, "Z": Z}
         if grad:
             def _spent(g, entry=entry):
@@ -148,6 +151,53 @@ def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
     mean, var, flags, _, _ = torch.ops.gpk.variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
                                                            float(jitter), save)
+    cache.note_consumers(mean, var)
+    cache.check_pending()
+    if return_linv:
+        return mean, var, flags, Linv
+    return mean, var, flags
+
+
+def _mean_params_batched(mean_module, O, D, device):
+    """(w, b0) of a multi-output layer's mean (DeepGP.py:42-45): ConstantMean(batch_shape=[O])
+    as w = 0, b0 (O,) (one gradient per output); LinearMean with weights (O, D, 1) per output,
+    or the reference's LinearMean(input_dims), (D, 1) weights and one bias shared by all outputs
+    (their gradients are summed over O)."""
+    if hasattr(mean_module, "weights"):
+        wt = mean_module.weights
+        w = wt.reshape(O, D) if wt.dim() == 3 else wt.reshape(D)
+        b = mean_module.bias
+        if b is None:
+            return w, torch.zeros(1, device=device)
+        return w, (b.reshape(O) if b.dim() == 2 else b.reshape(1))
+    if hasattr(mean_module, "constant"):
+        c = mean_module.constant
+        return torch.zeros(D, device=device), (c.reshape(O) if c.dim() == 2 else c.reshape(1))
+    raise NotImplementedError(f"mean module {type(mean_module).__name__} is not on the reference path "
+                              "(DeepGP.py:42-45: ConstantMean or LinearMean)")
+
+
+def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
+                                cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
+    """``variational_predict`` for the O independent output GPs of a multi-output layer, one
+    launch chain each way: x (B, N, D) shared by the outputs or (O, B, N, D), Z (O, M, D), vmean /
+    vstd (O, M), outputscale (O,), lengthscale (O, D) -> mean, var (O, B, N), one clamp flag for
+    all outputs (and Linv (O, M, M)). ``cache`` holds the (O, M, M) factor as ONE entry: reuse,
+    spent-marking and the pending psd_safe_cholesky verdict (a vector of O codes) work as for a
+    single output."""
+    O, _, D = Z.shape
+    w, b0 = _mean_params_batched(mean_module, O, D, x.device)
+    s2 = outputscale.reshape(O)
+    ls = lengthscale.reshape(O, -1)
+    vmean = vmean.reshape(O, -1)
+    vstd = vstd.reshape(O, -1)
+    if cache is None or key_tensors is None:
+        cache = KzzCache()
+        key_tensors = (Z, s2, ls)
+    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
+    mean, var, flags, _, _ = torch.ops.gpk.variational_fwd_batched(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
+                                                                   float(jitter), save)
     cache.note_consumers(mean, var)
     cache.check_pending()
     if return_linv:

@@ -304,6 +304,72 @@ int gpk_variational_adjoint_saved_f32(const float* X, const float* Z, const doub
                                       float* dZ, float* dpar, void* stream);
 
 /*
+ * Multi-output (batched) variational chain: O independent GPs of one DeepGP layer
+ * (output_dims = O: inducing points (O, M, D), q(u) batch (O,), kernel hyper-parameters per
+ * output) in ONE launch of every kernel -- the output index on grid dimension y, each
+ * output's workgroups exactly those of the single-output function at the same (B, N, M, D),
+ * so every result is bit-identical to O single-output calls. Every array of the
+ * single-output functions gains a dense leading O; 1 <= O <= 65535 (gridDim.y), B, N, M, D
+ * limited as there.
+ *
+ * Replaces (reference): ToyDeepGPHiddenLayer with output_dims = O
+ * (denoising_model/DeepGP.py:24-31: inducing points (O, M, D), batch_shape [O] on the
+ * variational distribution, mean and kernel) through upstream VariationalStrategy with a
+ * batch of GPs, and its autograd backward (train.py:166); SURVEY.md §8a rows a7-a11.
+ *
+ *   gpk_kzz_chol_f64_batched: gpk_kzz_chol_f64 per output -- O factor workgroups in one
+ *     launch (one CU each), T x O inverse workgroups in a second; the fp64 jitter ladder
+ *     restarts per output and reports in info[o].
+ *     Z : (O, M, D)   hyp : (O, 1 + D)   L, Linv : (O, M, M) double out   info : (O,) int out
+ *   gpk_kzz_backward_f64_batched: gpk_kzz_backward_f64 per output, each of its launches once.
+ *     dLinv, L, Linv : (O, M, M)   Z : (O, M, D)   hyp : (O, 1 + D)
+ *     workspace : gpk_kzz_backward_batched_workspace_bytes(O, M, D) bytes (O slices; 0 for an
+ *     unsupported shape)   dZ : (O, M, D) out   dhyp : (O, 1 + D) out
+ */
+int gpk_kzz_chol_f64_batched(const float* Z, const float* hyp, int O, int M, int D, float jitter,
+                             double chol_jitter, int max_tries, double* L, double* Linv, int* info,
+                             void* stream);
+size_t gpk_kzz_backward_batched_workspace_bytes(int O, int M, int D);
+int gpk_kzz_backward_f64_batched(const double* dLinv, const double* L, const double* Linv,
+                                 const float* Z, const float* hyp, int O, int M, int D, void* workspace,
+                                 float* dZ, float* dhyp, void* stream);
+
+/*
+ * gpk_variational_f32 / gpk_variational_train_f32 and their adjoints for O outputs at once
+ * (no y / ell: the ELBO terms of a multi-output layer are formed by the caller).
+ *   X : (B, N, D) read by every output when shared_x != 0 (the layer's own case: DeepGPLayer
+ *       expands its input over O with stride 0, so no (O, B, N, D) copy is made), else
+ *       (O, B, N, D)
+ *   Z : (O, M, D)   Linv : (O, M, M) double   vmean, vstd : (O, M)   hyp : (O, 4 + 2D)
+ *   mean, var : (O, B, N) float out   flags : (1,) int out or NULL, every output ORs into it
+ *   saved : NULL (inference forward / recompute adjoint) or O x
+ *       gpk_variational_saved_bytes(B, N, M, D) bytes (training forward; the adjoint then runs
+ *       from that state); non-NULL at a shape whose saved size is 0 is an argument error
+ *       (forward -16, adjoint -10)
+ *   gmean, gvar : (O, B, N)
+ *   workspace : gpk_variational_adjoint_batched_workspace_bytes(O, B, N, M, D, has_saved)
+ *       bytes, O slices of the single-output query (the saved-state one when has_saved != 0);
+ *       0 for an unsupported shape
+ *   dX : (O, B, N, D) float out, per output also with shared inputs (the caller sums over O)
+ *   dLinv : (O, M, M) double out   dZ : (O, M, D) out   dpar : (O, 2M + 2D + 2) out
+ * All sums keep the single-output order (run-to-run deterministic).
+ *
+ * Replaces (reference): DeepGPLayer.__call__ / VariationalStrategy.forward for
+ * ToyDeepGPHiddenLayer(output_dims = O) (denoising_model/DeepGP.py:24-31, 42-49) and the
+ * autograd backward train.py:166 runs through it; SURVEY.md §8a rows a9-a11, §8f row 1.
+ */
+int gpk_variational_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                const float* vmean, const float* vstd, const float* hyp, int O, int B,
+                                int N, int M, int D, float* mean, float* var, int* flags, void* saved,
+                                void* stream);
+size_t gpk_variational_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D, int has_saved);
+int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                        const float* vmean, const float* vstd, const float* hyp,
+                                        const float* gmean, const float* gvar, const void* saved, int O,
+                                        int B, int N, int M, int D, void* workspace, float* dX,
+                                        double* dLinv, float* dZ, float* dpar, void* stream);
+
+/*
  * GPU-resident training-window gather:
  *   for window b with first row r = rows[b] of the (id, time)-sorted table:
  *     enc[b] = table[r      : r + n_enc]                  (n_enc, F)

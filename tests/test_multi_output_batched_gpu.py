@@ -1,0 +1,475 @@
+"""The multi-output (batched) variational chain: O independent output GPs in ONE launch of
+every kernel (gpk_*_batched, the output index on grid dimension y).
+
+Every batched result must be bit-identical to O single-output calls (each output's workgroups
+are the single-output launcher's) and within the project's 1e-4 (norm-wise per window / per
+gradient block) of the fp64 oracle called once per output. Inputs: seeded draws scaled
+randn / sqrt(D) as the _case helpers of test_variational_gpu.py / test_variational_grad_gpu.py.
+"""
+import math
+import types
+import warnings
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from oracle import gp_oracle as O
+
+pytestmark = pytest.mark.gpu
+LN2 = math.log(2.0)
+TOL = 1e-4
+NO = 3
+# one shape per kernel path: register (N under one chunk), register (ragged M, N crossing a
+# chunk), LDS-tiled (D > 32), M > 64 with the saved state, M > 64 with the 64-wide D variant
+SHAPES = [(3, 20, 8, 4), (2, 40, 24, 8), (2, 30, 48, 48), (2, 40, 96, 4), (2, 33, 100, 40)]
+
+
+def _rel_rows(a, b):
+    a = np.asarray(a, np.float64).reshape(a.shape[0], -1)
+    b = np.asarray(b, np.float64).reshape(b.shape[0], -1)
+    return float((np.linalg.norm(a - b, axis=1) / np.linalg.norm(b, axis=1)).max())
+
+
+def _rel(a, b):
+    a = np.asarray(a, np.float64).ravel()
+    b = np.asarray(b, np.float64).ravel()
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def _hyper(no, D):
+    """Distinct outputscale and ARD lengthscales per output: the 0.7 .. 1.3 range of
+    test_variational_grad_gpu.py, shifted per output and, below D = 16, shortened by sqrt(D / 16).
+    Inputs drawn randn / sqrt(D) lie on a D-dimensional cloud of unit radius whatever D is, so at
+    D = 4 the 96 inducing points of the M > 64 shape sit within one unit lengthscale of each
+    other: cond(K_ZZ + 1e-4 I) is then 2.5e5 .. 5.5e5 and the reference's OWN fp32 arithmetic
+    (tests/test_variational_grad_gpu.py::_fp32_reference_grads: GPyTorch's fp32 kernel with the
+    fp64 Cholesky / solve) is 1e-4 .. 2.4e-4 off the fp64 oracle on dZ -- the regime
+    test_variational_grads_ill_conditioned_kzz covers with its own rule. A 1e-4 bound against
+    the fp64 oracle says something about the kernels only where fp32 arithmetic itself is inside
+    it, so the lengthscales keep the reference's own error at least 3x inside the bound at every
+    shape (<= 2.9e-5; _oracle_grads asserts it on the CPU)."""
+    s2 = torch.linspace(0.6, 1.1, no)
+    ls = torch.stack([torch.linspace(0.7 + 0.1 * o, 1.3 - 0.05 * o, D) for o in range(no)])
+    return s2, ls * min(1.0, math.sqrt(D / 16.0))
+
+
+def _case(no, B, N, M, D, seed, shared):
+    """Per-output hyper-parameters, a trained-like q(u), a per-output LinearMean."""
+    g = torch.Generator().manual_seed(seed)
+    X = torch.randn(*(() if shared else (no,)), B, N, D, generator=g) / math.sqrt(D)
+    Z = torch.randn(no, M, D, generator=g) / math.sqrt(D)
+    m = 0.3 * torch.randn(no, M, generator=g)
+    s = 0.5 + 0.5 * torch.rand(no, M, generator=g)
+    w = torch.randn(no, D, generator=g)
+    b0 = torch.randn(no, generator=g)
+    s2, ls = _hyper(no, D)
+    return X, Z, m, s, w, b0, s2, ls
+
+
+def _pack(ops, s2, ls, w, b0, var_jitter, dev):
+    """(O, 4 + 2D) hyper rows from the single-output packer (var_jitter: one value per output)."""
+    no, D = ls.shape
+    return torch.stack([ops.pack_variational_hyper(float(s2[o]), 1.0, float(var_jitter[o]), float(b0[o]),
+                                                   w[o].to(dev), ls[o].to(dev), D, dev) for o in range(no)])
+
+
+def _kzz_hyper(s2, ls):
+    return torch.cat([s2.reshape(-1, 1), ls], dim=1)
+
+
+# ---------------------------------------------------------------------------
+# 1. factor
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("M,D", [(24, 8), (96, 4), (130, 16)])
+def test_batched_factor_bit_identical_and_vs_oracle(cuda_device, M, D):
+    from fine_grained_gaussian_process_forcasting_amd import ops
+    dev = cuda_device
+    g = torch.Generator().manual_seed(M + D)
+    Z = torch.randn(NO, M, D, generator=g) / math.sqrt(D)
+    s2, ls = _hyper(NO, D)
+    fb = ops.kzz_cholesky_batched(Z.to(dev), _kzz_hyper(s2, ls).to(dev), jitter=1e-4)
+    assert fb.L.shape == (NO, M, M) and fb.Linv.shape == (NO, M, M) and fb.info.shape == (NO,)
+    for o in range(NO):
+        f1 = ops.kzz_cholesky(Z[o].to(dev), float(s2[o]), ls[o].to(dev), jitter=1e-4)
+        assert torch.equal(fb.L[o], f1.L) and torch.equal(fb.Linv[o], f1.Linv), o
+        assert int(fb.info[o]) == int(f1.info.item()) == 0
+        Kzz = O.rbf(Z[o].double().numpy(), Z[o].double().numpy(), ls[o].double().numpy(), float(s2[o]),
+                    x1_eq_x2=True, zero_diag=False)
+        Kzz[np.arange(M), np.arange(M)] += 1e-4
+        Lref = np.linalg.cholesky(Kzz)
+        e = np.linalg.norm(fb.L[o].cpu().numpy() - Lref) / np.linalg.norm(Lref)
+        print(f"M={M} D={D} o={o} L rel {e:.2e}")
+        assert e <= TOL, (o, e)
+
+
+# ---------------------------------------------------------------------------
+# 2. the fp64 jitter ladder restarts per output
+# ---------------------------------------------------------------------------
+def test_batched_factor_ladder_per_output(cuda_device):
+    from fine_grained_gaussian_process_forcasting_amd import NumericalWarning, ops
+    dev = cuda_device
+    M, D = 48, 8
+    ls = np.full(D, LN2)
+    Zs = []
+    for seed in (200, 202):      # well separated: factor without jitter
+        Zo = torch.randn(M, D, generator=torch.Generator().manual_seed(seed)) / math.sqrt(D)
+        K = O.rbf(Zo.double().numpy(), Zo.double().numpy(), ls, LN2, x1_eq_x2=True, zero_diag=False)
+        assert np.linalg.eigvalsh(K.astype(np.float32).astype(np.float64)).min() >= 0.02
+        Zs.append(Zo)
+    g = torch.Generator().manual_seed(123)      # test_kzz_fp64_jitter_ladder's near-duplicate set
+    z0 = torch.randn(1, D, generator=g)
+    Zdup = z0 + 1e-4 * torch.randn(M, D, generator=g)
+    Z = torch.stack([Zs[0], Zdup, Zs[1]])
+    hyp = torch.full((NO, 1 + D), LN2)
+    f = ops.kzz_cholesky_batched(Z.to(dev), hyp.to(dev), jitter=0.0)
+    info = f.info.cpu().tolist()
+    assert info[0] == 0 and info[2] == 0 and info[1] < 0, info
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        ops.check_cholesky_info(f.info, 1e-8)
+    msgs = [str(x.message) for x in w if issubclass(x.category, NumericalWarning)]
+    assert len(msgs) == -info[1] and msgs[0] == "A not p.d., added jitter of 1.0e-08 to the diagonal"
+    total = sum(1e-8 * 10 ** i - (1e-8 * 10 ** (i - 1) if i else 0.0) for i in range(-info[1]))
+    for o, tot in ((0, 0.0), (1, total), (2, 0.0)):
+        K = O.rbf(Z[o].double().numpy(), Z[o].double().numpy(), ls, LN2, x1_eq_x2=True, zero_diag=False)
+        L = f.L[o].cpu().numpy()
+        resid = np.abs(L @ L.T - (K + tot * np.eye(M))).max()
+        assert resid <= 1e-6, (o, resid)       # fp32 rounding of K's entries is ~1e-7
+
+
+# ---------------------------------------------------------------------------
+# 3. forward
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("shared", [True, False])
+@pytest.mark.parametrize("B,N,M,D", SHAPES)
+def test_batched_forward_bit_identical_and_vs_oracle(cuda_device, B, N, M, D, shared):
+    from fine_grained_gaussian_process_forcasting_amd import _native, ops
+    dev = cuda_device
+    X, Z, m, s, w, b0, s2, ls = _case(NO, B, N, M, D, seed=7 * B + N + M, shared=shared)
+    fb = ops.kzz_cholesky_batched(Z.to(dev), _kzz_hyper(s2, ls).to(dev), jitter=1e-4)
+    hyper = _pack(ops, s2, ls, w, b0, [1e-4] * NO, dev)
+    Xd, Zd, md, sd = X.to(dev), Z.to(dev), m.to(dev), s.to(dev)
+    has_saved = _native.lib().gpk_variational_saved_bytes(B, N, M, D) > 0
+    for save in ([False, True] if has_saved else [False]):
+        out = ops.variational_forward_batched(Xd, Zd, fb.Linv, md, sd, hyper, save=save)
+        assert out.mean.shape == (NO, B, N) and out.var.shape == (NO, B, N)
+        assert (out.saved is not None) == save
+        flag, saved = 0, []
+        for o in range(NO):
+            xo = Xd if shared else Xd[o]
+            one = ops.variational_forward(xo, Zd[o], fb.Linv[o], md[o], sd[o], hyper=hyper[o], save=save)
+            assert torch.equal(out.mean[o], one.mean) and torch.equal(out.var[o], one.var), (o, save)
+            flag |= int(one.flags.item())
+            saved.append(one.saved)
+        assert int(out.flags.item()) == flag == 0
+        if save:
+            assert torch.equal(out.saved, torch.cat(saved))
+    for o in range(NO):
+        xo = X if shared else X[o]
+        ref = O.variational_forward(xo.double().numpy(), Z[o].double().numpy(), ls[o].double().numpy(),
+                                    float(s2[o]), w[o].double().numpy(), float(b0[o]), m[o].double().numpy(),
+                                    s[o].double().numpy(), jitter=1e-4, dtype=np.float64)
+        em = _rel_rows(out.mean[o].cpu().numpy(), ref.mean)
+        ev = _rel_rows(out.var[o].cpu().numpy(), ref.var)
+        print(f"B={B} N={N} M={M} D={D} shared={shared} o={o} mean {em:.2e} var {ev:.2e}")
+        assert em <= TOL and ev <= TOL, (o, em, ev)
+
+
+def test_batched_clamp_flag_is_or_of_outputs(cuda_device):
+    """The negative K_XX jitter hook of test_variance_clamp_flag_and_warning on output 1 only: its
+    variance clamps, the others' do not, and the one flag word carries the OR."""
+    from fine_grained_gaussian_process_forcasting_amd import ops
+    dev = cuda_device
+    B, N, M, D = 4, 64, 32, 8
+    X, Z, m, s, w, b0, s2, ls = _case(NO, B, N, M, D, seed=9, shared=True)
+    s[1] = 0.1 + 0.2 * torch.rand(M, generator=torch.Generator().manual_seed(1))
+    s2[1], ls[1] = LN2, LN2      # that test's kernel hyper-parameters: about two thirds of the points clamp
+    fb = ops.kzz_cholesky_batched(Z.to(dev), _kzz_hyper(s2, ls).to(dev), jitter=1e-4)
+    hyper = _pack(ops, s2, ls, w, b0, [1e-4, -0.4, 1e-4], dev)
+    Xd, Zd, md, sd = X.to(dev), Z.to(dev), m.to(dev), s.to(dev)
+    out = ops.variational_forward_batched(Xd, Zd, fb.Linv, md, sd, hyper)
+    flags = []
+    for o in range(NO):
+        one = ops.variational_forward(Xd, Zd[o], fb.Linv[o], md[o], sd[o], hyper=hyper[o])
+        assert torch.equal(out.mean[o], one.mean) and torch.equal(out.var[o], one.var), o
+        flags.append(int(one.flags.item()))
+    assert flags == [0, 1, 0] and int(out.flags.item()) == 1
+    ref = O.variational_forward(X.double().numpy(), Z[1].double().numpy(), ls[1].double().numpy(), float(s2[1]),
+                                w[1].double().numpy(), float(b0[1]), m[1].double().numpy(), s[1].double().numpy(),
+                                jitter=1e-4, dtype=np.float64, var_jitter=-0.4)
+    frac = float((ref.var <= 1e-6).mean())
+    assert 0.05 < frac < 0.95, frac
+    assert np.abs(out.var[1].cpu().numpy() - ref.var).max() <= 1e-5
+
+
+# ---------------------------------------------------------------------------
+# 4. backward
+# ---------------------------------------------------------------------------
+def _grad_case(B, N, M, D):
+    g = torch.Generator().manual_seed(B * 1000 + N + M)
+    X = torch.randn(B, N, D, generator=g) / np.sqrt(D)
+    Z = torch.randn(NO, M, D, generator=g) / np.sqrt(D)
+    m = 0.3 * torch.randn(NO, M, generator=g)
+    s = 0.5 + 0.5 * torch.rand(NO, M, generator=g)
+    w = torch.randn(D, generator=g)          # the reference's LinearMean(input_dims): shared by the outputs
+    b0 = 0.3
+    s2, ls = _hyper(NO, D)
+    gmean = torch.randn(NO, B, N, generator=g)
+    gvar = torch.randn(NO, B, N, generator=g)
+    return X, Z, m, s, w, b0, s2, ls, gmean, gvar
+
+
+_ORACLE_GRADS = {}
+
+
+def _oracle_grads(B, N, M, D):
+    """Per-output oracle gradients, computed once per shape; X, weights and bias (shared by the
+    outputs) summed over O."""
+    key = (B, N, M, D)
+    if key not in _ORACLE_GRADS:
+        from tests.test_variational_grad_gpu import _fp32_reference_grads
+        X, Z, m, s, w, b0, s2, ls, gmean, gvar = _grad_case(B, N, M, D)
+        per = [O.variational_grads(X.double().numpy(), Z[o].double().numpy(), ls[o].double().numpy(), float(s2[o]),
+                                   w.double().numpy(), b0, m[o].double().numpy(), s[o].double().numpy(),
+                                   gmean[o].double().numpy(), gvar[o].double().numpy(), jitter=1e-4)
+               for o in range(NO)]
+        # the cases are inside the regime the bound is meant for (see _hyper): the reference's own
+        # fp32 arithmetic is at least 3x inside it on every gradient block of every output
+        for o in range(NO):
+            f32 = _fp32_reference_grads(X.numpy(), Z[o].numpy(), ls[o].numpy(), float(s2[o]), w.numpy(), b0,
+                                        m[o].numpy(), s[o].numpy(), gmean[o].numpy(), gvar[o].numpy())
+            for k in ("X", "Z", "m", "s", "outputscale", "lengthscale", "weights", "bias"):
+                assert _rel(f32[k], per[o][k]) <= TOL / 3, (key, o, k)
+        ref = {k: np.stack([np.asarray(p[k], np.float64) for p in per])
+               for k in ("Z", "m", "s", "outputscale", "lengthscale")}
+        for k in ("X", "weights", "bias"):
+            ref[k] = sum(np.asarray(p[k], np.float64) for p in per)
+        _ORACLE_GRADS[key] = ref
+    return _ORACLE_GRADS[key]
+
+
+@pytest.mark.parametrize("B,N,M,D", SHAPES)
+def test_batched_grads_vs_oracle_and_deterministic(cuda_device, B, N, M, D):
+    """variational_predict_batched (the saved-state pair wherever it serves the shape) -> every
+    gradient block vs the oracle; two runs are bit-identical."""
+    from fine_grained_gaussian_process_forcasting_amd import ops_autograd
+    dev = cuda_device
+    X, Z, m, s, w, b0, s2, ls, gmean, gvar = _grad_case(B, N, M, D)
+    runs = []
+    for _ in range(2):
+        P = lambda t: t.clone().to(dev).requires_grad_(True)  # noqa: E731
+        Xd, Zd, md, sd, wd, s2d, lsd = P(X), P(Z), P(m), P(s), P(w.reshape(D, 1)), P(s2), P(ls)
+        b0d = torch.full((1,), b0, device=dev, requires_grad=True)
+        mm = types.SimpleNamespace(weights=wd, bias=b0d)
+        mean, var, flag = ops_autograd.variational_predict_batched(Xd, Zd, md, sd, s2d, lsd, mm, 1e-4)
+        assert mean.shape == (NO, B, N) and int(flag.item()) == 0
+        ((gmean.to(dev) * mean).sum() + (gvar.to(dev) * var).sum()).backward()
+        runs.append({"X": Xd.grad, "Z": Zd.grad, "m": md.grad, "s": sd.grad, "outputscale": s2d.grad,
+                     "lengthscale": lsd.grad, "weights": wd.grad, "bias": b0d.grad})
+    ref = _oracle_grads(B, N, M, D)
+    for k, v in runs[0].items():
+        assert torch.equal(v, runs[1][k]), k
+        e = _rel(v.detach().cpu().numpy(), ref[k])
+        print(f"B={B} N={N} M={M} D={D} {k:12s} {e:.2e}")
+        assert e <= TOL, (k, e)
+
+
+@pytest.mark.parametrize("B,N,M,D", SHAPES)
+def test_batched_recompute_adjoint_vs_oracle_and_single(cuda_device, B, N, M, D):
+    """The recompute adjoint (saved = None) at every shape, composed at the op level with the
+    batched K_ZZ adjoint: bit-identical to O single-output calls, gradients vs the oracle."""
+    from fine_grained_gaussian_process_forcasting_amd import ops
+    dev = cuda_device
+    X, Z, m, s, w, b0, s2, ls, gmean, gvar = _grad_case(B, N, M, D)
+    kh = _kzz_hyper(s2, ls).to(dev)
+    Xd, Zd, md, sd, gm, gv = (t.to(dev) for t in (X, Z, m, s, gmean, gvar))
+    fb = ops.kzz_cholesky_batched(Zd, kh, jitter=1e-4)
+    hyper = _pack(ops, s2, ls, w.expand(NO, D), torch.full((NO,), b0), [1e-4] * NO, dev)
+    adj = ops.variational_adjoint_batched(Xd, Zd, fb.Linv, md, sd, hyper, gm, gv, saved=None)
+    dZk, dhk = ops.kzz_backward_batched(adj.dLinv, fb.L, fb.Linv, Zd, kh)
+    for o in range(NO):
+        one = ops.variational_adjoint(Xd, Zd[o], fb.Linv[o], md[o], sd[o], hyper[o], gm[o], gv[o])
+        assert torch.equal(adj.dX[o], one.dX) and torch.equal(adj.dLinv[o], one.dLinv), o
+        assert torch.equal(adj.dZ[o], one.dZ) and torch.equal(adj.dpar[o], one.dpar), o
+        kz, ks2, kls = ops.kzz_backward(one.dLinv, fb.L[o], fb.Linv[o], Zd[o], s2[o].to(dev), ls[o].to(dev))
+        assert torch.equal(dZk[o], kz) and torch.equal(dhk[o, 0], ks2) and torch.equal(dhk[o, 1:], kls), o
+    dp = adj.dpar.double()
+    got = {"X": adj.dX.sum(0), "Z": adj.dZ.double() + dZk, "m": dp[:, :M], "s": dp[:, M:2 * M],
+           "outputscale": dp[:, 2 * M] + dhk[:, 0], "lengthscale": dp[:, 2 * M + 1:2 * M + 1 + D] + dhk[:, 1:],
+           "weights": dp[:, 2 * M + 1 + D:2 * M + 1 + 2 * D].sum(0), "bias": dp[:, 2 * M + 1 + 2 * D].sum()}
+    ref = _oracle_grads(B, N, M, D)
+    for k, v in got.items():
+        e = _rel(v.detach().cpu().numpy(), ref[k])
+        print(f"recompute B={B} N={N} M={M} D={D} {k:12s} {e:.2e}")
+        assert e <= TOL, (k, e)
+
+
+# ---------------------------------------------------------------------------
+# 5. the layer: one launch chain per call, one factor and one K_ZZ adjoint per step
+# ---------------------------------------------------------------------------
+def _layer(mean_type, dev, d=8, M=24):
+    from fine_grained_gaussian_process_forcasting_amd.denoising_model.DeepGP import ToyDeepGPHiddenLayer
+    layer = ToyDeepGPHiddenLayer(input_dims=d, output_dims=NO, seed=5, num_inducing=M, mean_type=mean_type).to(dev)
+    with torch.no_grad():   # distinct hyper-parameters per output
+        layer.covar_module.raw_outputscale.copy_(torch.tensor([0.0, 0.4, -0.3]))
+        layer.covar_module.base_kernel.raw_lengthscale.add_(torch.linspace(-0.3, 0.3, NO).reshape(NO, 1, 1).to(dev))
+    return layer
+
+
+def _layer_params(layer, o):
+    """(Z, ls, s2, w, b0, m, s) of output o as float64 numpy (as tests/test_models_gpu.py)."""
+    vs = layer.variational_strategy
+    q = vs._variational_distribution
+    f = lambda t: t.detach().cpu().double().numpy()  # noqa: E731
+    mm = layer.mean_module
+    if hasattr(mm, "weights"):
+        w, b0 = f(mm.weights).reshape(-1), float(mm.bias.item())
+    else:
+        w, b0 = np.zeros(vs.inducing_points.shape[-1]), float(f(mm.constant).reshape(-1)[o])
+    return (f(vs.inducing_points)[o], f(layer.covar_module.base_kernel.lengthscale)[o].reshape(-1),
+            float(f(layer.covar_module.outputscale)[o]), w, b0, f(q.variational_mean)[o], f(q._variational_stddev)[o])
+
+
+class _LayerModel(nn.Module):
+    """The layer + a Gaussian likelihood: one training step calls the layer twice (N = 20 and
+    N = 12, as denoise_model_2 calls its GP on the encoder and decoder windows)."""
+
+    def __init__(self, mean_type, dev):
+        super().__init__()
+        from fine_grained_gaussian_process_forcasting_amd.gp import GaussianLikelihood, _DeepGPVariationalStrategy
+        self.layer = _layer(mean_type, dev)
+        self.likelihood = GaussianLikelihood().to(dev)
+        self.variational_strategy = _DeepGPVariationalStrategy(self)
+
+    def forward(self, x1, x2, y1, g2):
+        from fine_grained_gaussian_process_forcasting_amd.mlls import DeepApproximateMLL, VariationalELBO
+        o1, o2 = self.layer(x1), self.layer(x2)
+        elbo = DeepApproximateMLL(VariationalELBO(self.likelihood, self, 8))(o1, y1)
+        return -elbo.mean() + (g2 * o2.mean).mean() + (g2 * o2.variance).mean()
+
+
+def _layer_batch(dev, seed=1, b=4, d=8):
+    g = torch.Generator().manual_seed(seed)
+    x1 = torch.randn(b, 20, d, generator=g) / math.sqrt(d)
+    x2 = torch.randn(b, 12, d, generator=g) / math.sqrt(d)
+    y1 = torch.randn(1, b, 20, NO, generator=g)
+    g2 = torch.randn(1, b, 12, NO, generator=g)
+    return tuple(t.to(dev) for t in (x1, x2, y1, g2))
+
+
+@pytest.mark.parametrize("mean_type", ["constant", "linear"])
+def test_layer_runs_one_launch_chain(cuda_device, monkeypatch, mean_type):
+    from fine_grained_gaussian_process_forcasting_amd import ops, settings
+    dev = cuda_device
+    calls = {}
+    for name in ("kzz_cholesky_batched", "variational_forward_batched", "kzz_backward_batched",
+                 "variational_adjoint_batched", "kzz_cholesky", "variational_forward"):
+        def counted(*a, _real=getattr(ops, name), _name=name, **k):
+            calls[_name] = calls.get(_name, 0) + 1
+            return _real(*a, **k)
+        calls[name] = 0
+        monkeypatch.setattr(ops, name, counted)
+    model = _LayerModel(mean_type, dev)
+    layer = model.layer
+    x1, x2, y1, g2 = _layer_batch(dev)
+    opt = torch.optim.SGD(model.parameters(), lr=1e-3)
+    with settings.num_likelihood_samples(1):
+        out = layer(x1)
+        # outputs vs the oracle, per output (as test_multi_output_layer_vs_oracle)
+        assert out.mean.shape == (1, 4, 20, NO) and out.event_shape == (20, NO)
+        xn = x1.cpu().double().numpy()
+        for o in range(NO):
+            ref = O.variational_forward(xn, *_layer_params(layer, o), jitter=1e-4, dtype=np.float64)
+            assert _rel_rows(out.mean[0, ..., o].detach().cpu().numpy(), ref.mean) <= TOL, o
+            assert _rel_rows(out.variance[0, ..., o].detach().cpu().numpy(), ref.var) <= TOL, o
+        del out
+        layer.variational_strategy._kzz_cache.clear()
+        for k in calls:
+            calls[k] = 0
+        # one training step, two layer calls: one factor, two forwards, no single-output launch
+        loss = model(x1, x2, y1, g2)
+        assert calls["kzz_cholesky_batched"] == 1 and calls["variational_forward_batched"] == 2
+        assert calls["kzz_cholesky"] == 0 and calls["variational_forward"] == 0
+        loss.backward()
+        assert calls["kzz_backward_batched"] == 1 and calls["variational_adjoint_batched"] == 2
+        for name, p in model.named_parameters():
+            assert p.grad is not None and torch.isfinite(p.grad).all() and p.grad.abs().sum() > 0, name
+        opt.step()                      # the parameters changed: the next call refactors
+        layer(x1)
+        assert calls["kzz_cholesky_batched"] == 2
+        model.eval()                    # eval / no-grad: one factor reused across batches
+        with torch.no_grad():
+            layer(x1)
+            layer(x2)
+            layer(x1[:2])
+        assert calls["kzz_cholesky_batched"] == 3 and calls["kzz_cholesky"] == 0
+
+
+# ---------------------------------------------------------------------------
+# 6. opcheck
+# ---------------------------------------------------------------------------
+def test_batched_custom_ops_opcheck(cuda_device):
+    import fine_grained_gaussian_process_forcasting_amd.library  # noqa: F401
+    dev = cuda_device
+    g = torch.Generator().manual_seed(0)
+    B, N, M, D, no = 2, 24, 8, 4, 2
+    tests = ("test_schema", "test_autograd_registration", "test_faketensor")
+    X = (torch.randn(B, N, D, generator=g) / 2).to(dev)
+    Z = (torch.randn(no, M, D, generator=g) / 2).to(dev)
+    s2 = torch.tensor([0.8, 0.6], device=dev)
+    ls = torch.full((no, D), 0.7, device=dev)
+    torch.library.opcheck(torch.ops.gpk.kzz_factor_batched.default, (Z, s2, ls, 1e-4, 1e-8, 3), test_utils=tests)
+    Linv = torch.ops.gpk.kzz_factor_batched(Z, s2, ls, 1e-4, 1e-8, 3)[0]
+    vm = (1e-3 * torch.randn(no, M, generator=g)).to(dev)
+    args = (X, Linv, Z, vm, torch.ones(no, M, device=dev), s2, ls, torch.randn(D, generator=g).to(dev),
+            torch.tensor([0.1], device=dev), 1e-4)
+    torch.library.opcheck(torch.ops.gpk.variational_fwd_batched.default, args, test_utils=tests)
+    mean, var, _, hyp, saved = torch.ops.gpk.variational_fwd_batched(*args)
+    adj_args = (X, Linv, Z, vm, args[4], hyp, torch.randn_like(mean), torch.randn_like(var), saved)
+    torch.library.opcheck(torch.ops.gpk.variational_adj_batched.default, adj_args, test_utils=tests)
+    # with gradients requested, the registered autograd formulas are exercised
+    Zr = Z.clone().requires_grad_(True)
+    torch.library.opcheck(torch.ops.gpk.kzz_factor_batched.default, (Zr, s2, ls, 1e-4, 1e-8, 3),
+                          test_utils=("test_autograd_registration",))
+    Xr = X.clone().requires_grad_(True)
+    torch.library.opcheck(torch.ops.gpk.variational_fwd_batched.default, (Xr,) + args[1:],
+                          test_utils=("test_autograd_registration",))
+
+
+# ---------------------------------------------------------------------------
+# 7. HIP-graph capture of the O = 3 training step
+# ---------------------------------------------------------------------------
+def test_graphed_multi_output_step_matches_eager(cuda_device):
+    from fine_grained_gaussian_process_forcasting_amd import settings
+    from fine_grained_gaussian_process_forcasting_amd.graphs import GraphedStep
+    dev = cuda_device
+    batches = [_layer_batch(dev, seed=20 + k) for k in range(4)]
+    with settings.num_likelihood_samples(1):
+        ma = _LayerModel("linear", dev)
+        mb = _LayerModel("linear", dev)
+        with torch.no_grad():
+            ma(*batches[0])          # q(u) initialises lazily on the first call (its own randn)
+        mb.load_state_dict(ma.state_dict())
+        oa = torch.optim.SGD(ma.parameters(), lr=1e-2)
+        ob = torch.optim.SGD(mb.parameters(), lr=1e-2)
+
+        def eager(batch):
+            oa.zero_grad(set_to_none=True)
+            loss = ma(*batch)
+            loss.backward()
+            oa.step()
+            return float(loss.detach())
+
+        for _ in range(3):                       # GraphedStep's warm-up steps
+            eager(batches[0])
+        step = GraphedStep(mb, ob, batches[0], warmup=3)
+        for k in range(1, 4):
+            la = eager(batches[k])
+            lb = float(step(*batches[k]).detach())
+            assert math.isfinite(lb)
+            assert abs(la - lb) <= 1e-5 * max(1.0, abs(la)), (k, la, lb)
+        for (na, pa), (nb, pb) in zip(ma.named_parameters(), mb.named_parameters()):
+            assert na == nb
+            assert torch.allclose(pa, pb, rtol=1e-4, atol=1e-6), na
