@@ -36,6 +36,10 @@ SIGNATURES = {
                                        c_void_p]),
     "gpk_exact_posterior_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                         c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gpk_exact_posterior_cov_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gpk_exact_posterior_cov_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                            c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
     "gpk_kzz_chol_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_double, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_backward_workspace_bytes": (c_size_t, [c_int, c_int]),

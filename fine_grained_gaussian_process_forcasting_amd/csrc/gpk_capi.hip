@@ -4,10 +4,11 @@
 #include "gpk_internal.h"
 #include "gpk_elbo.h"
 #include "gpk_kzz.h"
+#include "gpk_posterior_cov.h"
 
 extern "C" {
 
-int gpk_version(void) { return 200; }
+int gpk_version(void) { return 300; }
 
 const char* gpk_strerror(int code) {
   if (code == 0) return "success";
@@ -91,6 +92,46 @@ int gpk_exact_posterior_f32(const float* X, const float* L, const float* z, cons
   GpkPostArgs a{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var};
   if (N > kGpkExactRegMaxN) return gpk_launch_exact_large_posterior(a, (hipStream_t)stream);
   return gpk_launch_exact_posterior(a, (hipStream_t)stream);
+}
+
+size_t gpk_exact_posterior_cov_workspace_bytes(int B, int N, int Ns) {
+  if (B < 0 || N < 1 || N > gpk_exact_max_n() || Ns < 0) return 0;
+  if (N > kGpkExactRegMaxN && B > 65535) return 0;
+  return gpk_post_cov_ws_floats(B, N, Ns) * sizeof(float);
+}
+
+int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
+                                void* workspace, float* mean, float* var, float* cov, void* stream) {
+  if (X == nullptr) return -1;
+  if (L == nullptr) return -2;
+  if (z == nullptr) return -3;
+  if (hyp == nullptr) return -4;
+  if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (Xs == nullptr) return -6;
+  if (B < 0) return -7;
+  if (N < 1 || N > gpk_exact_max_n()) return -8;
+  if (Ns < 0) return -9;
+  if (D < 1 || D > 64) return -10;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -11;   // V rows are read 16 B at a time
+  if (mean == nullptr) return -12;
+  if (var == nullptr) return -13;
+  if (cov == nullptr) return -14;
+  if (B == 0 || Ns == 0) return 0;
+  if (N > kGpkExactRegMaxN && B > 65535) return -7;   // the blocked kernel keeps B on gridDim.y
+  const int vs = gpk_post_cov_vstride(Ns);
+  float* V = (float*)workspace;
+  float* mu = V + (size_t)B * N * vs;   // after V: the workspace layout of gpk_posterior_cov.h
+  GpkPostVArgs a{};
+  static_cast<GpkPostArgs&>(a) = GpkPostArgs{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var};
+  a.V = V;
+  a.mu = mu;
+  a.vs = vs;
+  const int rc = N > kGpkExactRegMaxN ? gpk_launch_exact_large_posterior_storev(a, (hipStream_t)stream)
+                                      : gpk_launch_exact_posterior_storev(a, (hipStream_t)stream);
+  if (rc != 0) return rc;
+  GpkPostCovArgs c{hyp, n_lengthscale, Xs, V, mu, var, B, N, Ns, D, vs, cov};
+  return gpk_launch_exact_posterior_cov(c, (hipStream_t)stream);
 }
 
 int gpk_kzz_chol_f64(const float* Z, const float* hyp, int M, int D, float jitter,

@@ -31,6 +31,7 @@
 // lane's 8 operand values are 8 consecutive floats of one row.
 #include "gpk_common.h"
 #include "gpk_internal.h"
+#include "gpk_posterior_cov.h"
 
 #include <math.h>
 #include <mutex>
@@ -785,7 +786,11 @@ __host__ __device__ inline LgPostLds lg_post_layout(int Np) {
   return o;
 }
 
-__global__ void __launch_bounds__(kPostThreads) gpk_lg_post_kernel(GpkPostArgs a) {
+// STOREV (the joint-covariance call, gpk_posterior_cov.hip): the workgroup's 16 columns of V
+// also go to the workspace a.V, row-major (B, N, vs); columns >= Ns hold zeros (their K* is 0).
+// The window's first workgroup also stores the centring mean to a.mu (B, 64).
+template <bool STOREV>
+__global__ void __launch_bounds__(kPostThreads) gpk_lg_post_kernel(GpkPostArgsOf<STOREV> a) {
   extern __shared__ float smem[];
   const int b = blockIdx.y, t0 = 16 * blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int wave = wave_id_uniform();
@@ -807,6 +812,9 @@ __global__ void __launch_bounds__(kPostThreads) gpk_lg_post_kernel(GpkPostArgs a
   const int g = lane >> 4, c = lane & 15, q = lane >> 4, il = lane & 15;
 
   lg_centre(X, a.hyp, a.n_ls, N, Np, D, mu, ils, nrm, V, tid, kPostThreads);
+  if constexpr (STOREV) {
+    if (blockIdx.x == 0 && tid < D) a.mu[(size_t)b * 64 + tid] = mu[tid];
+  }
   if (tid < 16) {
     float s = 0.f;
     for (int d = 0; d < D; ++d) {
@@ -910,6 +918,14 @@ __global__ void __launch_bounds__(kPostThreads) gpk_lg_post_kernel(GpkPostArgs a
     a.mean[(size_t)b * Ns + t0 + tid] = cmean + (red[tid] + red[32 + tid]);
     a.var[(size_t)b * Ns + t0 + tid] = s2 - (red[16 + tid] + red[48 + tid]);
   }
+  if constexpr (STOREV) {
+    // every V row is final and visible (the barrier above); t0 + 15 < vs (a multiple of 64)
+    float* vout = a.V + (size_t)b * N * a.vs + t0;
+    for (int e = tid; e < 16 * N; e += kPostThreads) {
+      const int row = e >> 4, cc = e & 15;
+      vout[(size_t)row * a.vs + cc] = V[row * kVS + cc];
+    }
+  }
 }
 
 }  // namespace
@@ -949,11 +965,24 @@ int gpk_launch_exact_large_posterior(const GpkPostArgs& a, hipStream_t stream) {
   const size_t lds = (size_t)lg_post_layout(lg_np(a.N)).total * sizeof(float);
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute((const void*)gpk_lg_post_kernel,
+    (void)hipFuncSetAttribute((const void*)gpk_lg_post_kernel<false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipGetLastError();
   });
-  hipLaunchKernelGGL(gpk_lg_post_kernel, dim3((a.Ns + 15) / 16, a.B), dim3(kPostThreads), lds,
+  hipLaunchKernelGGL(gpk_lg_post_kernel<false>, dim3((a.Ns + 15) / 16, a.B), dim3(kPostThreads), lds,
+                     stream, a);
+  return (int)hipGetLastError();
+}
+
+int gpk_launch_exact_large_posterior_storev(const GpkPostVArgs& a, hipStream_t stream) {
+  const size_t lds = (size_t)lg_post_layout(lg_np(a.N)).total * sizeof(float);
+  static std::once_flag once;
+  std::call_once(once, [] {
+    (void)hipFuncSetAttribute((const void*)gpk_lg_post_kernel<true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipGetLastError();
+  });
+  hipLaunchKernelGGL(gpk_lg_post_kernel<true>, dim3((a.Ns + 15) / 16, a.B), dim3(kPostThreads), lds,
                      stream, a);
   return (int)hipGetLastError();
 }

@@ -23,6 +23,7 @@
 // No barrier after the prologue: the waves never exchange data.
 #include "gpk_common.h"
 #include "gpk_internal.h"
+#include "gpk_posterior_cov.h"
 
 #include <mutex>
 
@@ -57,8 +58,12 @@ GPK_DEVICE f32x4 mfma4(const f32x4 a, const f32x4 b, f32x4 d) {
 }
 
 // NB = ceil(N/16) block rows, DQ = DP/16 (DP = D padded to 16/32/64), FULL: N == 16*NB.
-template <int NB, int DQ, bool FULL>
-__global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgs a) {
+// STOREV (the joint-covariance call, gpk_posterior_cov.hip): each V tile also goes to the
+// workspace a.V, row-major (B, N, vs) with vs a multiple of kPostCols; dead test columns are
+// stored as zeros, rows >= N are not stored. The window's first tile also stores the centring
+// mean to a.mu (B, 64).
+template <int NB, int DQ, bool FULL, bool STOREV = false>
+__global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgsOf<STOREV> a) {
   extern __shared__ float smem[];
   constexpr int DP = 16 * DQ;
   constexpr int XS = DP + 4;
@@ -163,6 +168,9 @@ __global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgs a) {
     const int n = e / DP, d = e - n * DP;
     if (d < D) xtr[n * XS + d] -= red[256 + d];
   }
+  if constexpr (STOREV) {
+    if (tile == 0 && tid < DP) a.mu[(size_t)b * 64 + tid] = red[256 + tid];
+  }
   lds_barrier();
   for (int n = tid; n < NP; n += 256) {
     float s = 0.f;
@@ -261,6 +269,14 @@ __global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgs a) {
       mp = __builtin_fmaf(V[i][r], zz[r], mp);
       vp = __builtin_fmaf(V[i][r], V[i][r], vp);
     }
+    if constexpr (STOREV) {
+      float* vcol = a.V + (size_t)b * N * a.vs + tile * kPostCols + 16 * w + c;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * i + 4 * g + r;
+        if (FULL || row < N) vcol[(size_t)row * a.vs] = live ? V[i][r] : 0.f;
+      }
+    }
   }
   mp += __shfl_xor(mp, 16, 64);
   mp += __shfl_xor(mp, 32, 64);
@@ -272,8 +288,8 @@ __global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgs a) {
   }
 }
 
-template <int NB, int DQ>
-int launch_post(const GpkPostArgs& a, hipStream_t stream) {
+template <int NB, int DQ, bool STOREV>
+int launch_post(const GpkPostArgsOf<STOREV>& a, hipStream_t stream) {
   const PostLds lay = post_lds_layout(NB, 16 * DQ);
   const size_t lds = (size_t)lay.total * sizeof(float);
   const int T = (a.Ns + kPostCols - 1) / kPostCols;
@@ -282,28 +298,43 @@ int launch_post(const GpkPostArgs& a, hipStream_t stream) {
   if (a.N == 16 * NB) {
     static std::once_flag once;
     std::call_once(once, [&] {
-      (void)hipFuncSetAttribute((const void*)gpk_post_kernel<NB, DQ, true>,
+      (void)hipFuncSetAttribute((const void*)gpk_post_kernel<NB, DQ, true, STOREV>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipGetLastError();
     });
-    hipLaunchKernelGGL((gpk_post_kernel<NB, DQ, true>), dim3((unsigned)grid), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL((gpk_post_kernel<NB, DQ, true, STOREV>), dim3((unsigned)grid), dim3(256), lds,
+                       stream, a);
   } else {
     static std::once_flag once;
     std::call_once(once, [&] {
-      (void)hipFuncSetAttribute((const void*)gpk_post_kernel<NB, DQ, false>,
+      (void)hipFuncSetAttribute((const void*)gpk_post_kernel<NB, DQ, false, STOREV>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipGetLastError();
     });
-    hipLaunchKernelGGL((gpk_post_kernel<NB, DQ, false>), dim3((unsigned)grid), dim3(256), lds, stream, a);
+    hipLaunchKernelGGL((gpk_post_kernel<NB, DQ, false, STOREV>), dim3((unsigned)grid), dim3(256), lds,
+                       stream, a);
   }
   return (int)hipGetLastError();
 }
 
-template <int NB>
-int launch_post_nb(const GpkPostArgs& a, hipStream_t stream) {
-  if (a.D <= 16) return launch_post<NB, 1>(a, stream);
-  if (a.D <= 32) return launch_post<NB, 2>(a, stream);
-  return launch_post<NB, 4>(a, stream);
+template <int NB, bool STOREV>
+int launch_post_nb(const GpkPostArgsOf<STOREV>& a, hipStream_t stream) {
+  if (a.D <= 16) return launch_post<NB, 1, STOREV>(a, stream);
+  if (a.D <= 32) return launch_post<NB, 2, STOREV>(a, stream);
+  return launch_post<NB, 4, STOREV>(a, stream);
+}
+
+template <bool STOREV>
+int launch_post_any(const GpkPostArgsOf<STOREV>& a, hipStream_t stream) {
+  switch ((a.N + 15) / 16) {
+#define GPK_POST_CASE(nb) case nb: return launch_post_nb<nb, STOREV>(a, stream);
+    GPK_POST_CASE(1) GPK_POST_CASE(2) GPK_POST_CASE(3) GPK_POST_CASE(4)
+    GPK_POST_CASE(5) GPK_POST_CASE(6) GPK_POST_CASE(7) GPK_POST_CASE(8)
+    GPK_POST_CASE(9) GPK_POST_CASE(10) GPK_POST_CASE(11) GPK_POST_CASE(12)
+    GPK_POST_CASE(13) GPK_POST_CASE(14) GPK_POST_CASE(15) GPK_POST_CASE(16)
+#undef GPK_POST_CASE
+    default: return -6;
+  }
 }
 
 }  // namespace
@@ -315,13 +346,9 @@ size_t gpk_post_lds_bytes(int N, int D) {
 }
 
 int gpk_launch_exact_posterior(const GpkPostArgs& a, hipStream_t stream) {
-  switch ((a.N + 15) / 16) {
-#define GPK_POST_CASE(nb) case nb: return launch_post_nb<nb>(a, stream);
-    GPK_POST_CASE(1) GPK_POST_CASE(2) GPK_POST_CASE(3) GPK_POST_CASE(4)
-    GPK_POST_CASE(5) GPK_POST_CASE(6) GPK_POST_CASE(7) GPK_POST_CASE(8)
-    GPK_POST_CASE(9) GPK_POST_CASE(10) GPK_POST_CASE(11) GPK_POST_CASE(12)
-    GPK_POST_CASE(13) GPK_POST_CASE(14) GPK_POST_CASE(15) GPK_POST_CASE(16)
-#undef GPK_POST_CASE
-    default: return -6;
-  }
+  return launch_post_any<false>(a, stream);
+}
+
+int gpk_launch_exact_posterior_storev(const GpkPostVArgs& a, hipStream_t stream) {
+  return launch_post_any<true>(a, stream);
 }

@@ -10,7 +10,9 @@ models/exact_gp.py __call__ -> exact_prediction_strategies.py): the training fac
 and z = L^{-1}(y - c) come from gpk_exact_mll_f32 once and are cached until a
 parameter or the training data changes or ``train()`` is called (GPyTorch's
 ``prediction_strategy`` cache); mean and variance at x come from
-gpk_exact_posterior_f32. ``likelihood(model(x))`` adds the noise. As in GPyTorch,
+gpk_exact_posterior_f32, and the joint covariance (``covariance_matrix``, ``rsample``,
+``log_prob``) lazily from gpk_exact_posterior_cov_f32 on the same cached factor.
+``likelihood(model(x))`` adds the noise. As in GPyTorch,
 calling the model in eval mode on the training inputs warns (GPInputWarning) and
 returns the posterior there.
 
@@ -137,12 +139,23 @@ class ExactGPModel(nn.Module):
         if xs.shape[0] != Xb.shape[0]:
             xs = xs.expand(Xb.shape[0], *xs.shape[1:])
         from .. import library  # noqa: F401  (registers torch.ops.gpk)
-        mean, var = torch.ops.gpk.exact_posterior(Xb, L, z, hyper, xs.contiguous())
+        xs = xs.contiguous()
+        mean, var = torch.ops.gpk.exact_posterior(Xb, L, z, hyper, xs)
         if x.dim() == 3 or Xb.shape[0] > 1:
             shape = mean.shape                    # (B, Ns): one posterior per training window
         else:
             shape = x.shape[:-1] if x.dim() > 1 else x.shape
-        return MultivariateNormal(mean.reshape(shape), var.reshape(shape))
+        xs_d = xs.detach()
+        memo = []
+
+        def cov():
+            # the joint posterior, lazily as upstream (exact_predictive_covar): one
+            # gpk_exact_posterior_cov_f32 call on the cached factor, on first use only
+            if not memo:
+                memo.append(torch.ops.gpk.exact_posterior_cov(Xb, L, z, hyper, xs_d)[2])
+            return memo[0]
+
+        return MultivariateNormal(mean.reshape(shape), var.reshape(shape), covar_fn=cov)
 
     def _posterior_autograd(self, x):
         """The eval posterior WITH gradients (GPyTorch allows them; upstream
@@ -184,4 +197,6 @@ class ExactGPModel(nn.Module):
             shape = mean.shape
         else:
             shape = x.shape[:-1] if x.dim() > 1 else x.shape
-        return MultivariateNormal(mean.reshape(shape), var.reshape(shape))
+        # the joint posterior of the same restatement, differentiable: K** - V^T V
+        return MultivariateNormal(mean.reshape(shape), var.reshape(shape),
+                                  covar_fn=lambda: K[..., n:, n:] - V.transpose(-1, -2) @ V)

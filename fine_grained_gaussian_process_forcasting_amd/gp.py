@@ -255,15 +255,19 @@ class MultivariateNormal:
 
     @property
     def covariance_matrix(self):
-        """Dense prior covariance of an exact-GP / layer prior, materialised on request
-        (GPyTorch keeps covar_module(x) lazy and evaluates it here): outputscale * RBF with
-        upstream ``_sq_dist`` semantics (inputs centred by their mean, clamp at 0, exact 0 on
-        the diagonal) + the added likelihood noise on the diagonal. Not on the hot path: no
-        reference caller reads it. Variational outputs are diagonal-query (their marginals
-        are what the reference reads) and do not carry a covariance."""
+        """Dense covariance, materialised on request (GPyTorch keeps it lazy and evaluates it
+        here), + the added likelihood noise on the diagonal. Exact-GP / layer priors:
+        outputscale * RBF with upstream ``_sq_dist`` semantics (inputs centred by their mean,
+        clamp at 0, exact 0 on the diagonal). Distributions with a ``covar_fn``: what it
+        returns -- the exact posterior's K** - K*^T K_hat^{-1} K* (gpk_exact_posterior_cov_f32;
+        its diagonal is the unclamped variance, min_variance applies to ``.variance`` only, as
+        upstream) and the variational outputs' lazy covariance. Not on the hot path: no
+        reference caller reads it. A distribution built from a mean and marginal variances
+        alone carries no covariance."""
         if self._exact is None and self._covar_fn is None:
-            raise NotImplementedError("covariance_matrix is provided for exact-GP / layer priors and "
-                                      "variational outputs")
+            raise NotImplementedError("this distribution carries only marginal variances; "
+                                      "covariance_matrix is provided for exact-GP / layer priors, "
+                                      "the exact posterior and variational outputs")
         if self._exact is not None:
             X, lengthscale, outputscale, _ = self._exact
             K = rbf_covariance(X, lengthscale, outputscale)
@@ -280,6 +284,11 @@ class MultivariateNormal:
     @property
     def lazy_covariance_matrix(self):
         return self.covariance_matrix
+
+    def confidence_region(self):
+        """(mean - 2 stddev, mean + 2 stddev), as upstream MultivariateNormal.confidence_region."""
+        std2 = self.stddev.mul(2)
+        return self._mean.sub(std2), self._mean.add(std2)
 
     def rsample(self, sample_shape=torch.Size(), base_samples: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reparameterised sample mean + chol(Sigma) eps (upstream MultivariateNormal.rsample: the
@@ -333,9 +342,24 @@ class MultivariateNormal:
                                   preclamped=self._clamp_flag is not None or self._preclamped, covar_fn=sub)
 
     def log_prob(self, value: torch.Tensor) -> torch.Tensor:
-        """Exact-GP marginal log density (fused RBF + Cholesky + solve + logdet kernel)."""
+        """Exact-GP priors: the marginal log density by the fused RBF + Cholesky + solve + logdet
+        kernel. Distributions that carry a dense covariance (``covar_fn``: the exact posterior,
+        variational outputs): the Gaussian log density through R = psd_safe_cholesky(Sigma),
+        -0.5 (|R^{-1}(value - mean)|^2 + 2 sum log R_ii + n log 2 pi), as upstream
+        MultivariateNormal.log_prob (off the hot path: Sigma is materialised)."""
+        if self._exact is None and self._covar_fn is not None:
+            cov = self.covariance_matrix
+            root = psd_safe_cholesky(cov)
+            diff = (value - self._mean).unsqueeze(-1)
+            if diff.shape[:-2] != root.shape[:-2]:   # leading sample dimensions of value
+                root = root.expand(*diff.shape[:-2], *root.shape[-2:])
+            w = torch.linalg.solve_triangular(root, diff.to(root.dtype), upper=False).squeeze(-1)
+            n = self._mean.shape[-1]
+            logdet = 2.0 * root.diagonal(dim1=-2, dim2=-1).log().sum(-1)
+            return -0.5 * (w.pow(2).sum(-1) + logdet + n * math.log(2.0 * math.pi))
         if self._exact is None:
-            raise NotImplementedError("log_prob is provided for exact-GP outputs (GPModel.py)")
+            raise NotImplementedError("log_prob needs a covariance: an exact-GP prior (GPModel.py) "
+                                      "or a distribution with a dense covariance (covar_fn)")
         X, lengthscale, outputscale, constant = self._exact
         noise = self._added_noise if self._added_noise is not None else torch.zeros((), device=X.device)
         from .ops_autograd import exact_log_prob

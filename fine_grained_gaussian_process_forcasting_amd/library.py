@@ -9,6 +9,7 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::exact_mll(X, y, hyper, jitter, max_tries) -> (mll, L, z, info)         [autograd]
   gpk::exact_mll_grad(X, L, z, hyper, gout) -> (dX, dy, dhyp)
   gpk::exact_posterior(X, L, z, hyper, Xs) -> (mean, var)                     [eval only]
+  gpk::exact_posterior_cov(X, L, z, hyper, Xs) -> (mean, var, cov)            [eval only]
   gpk::kzz_factor(Z, s2, ls, jitter, chol_jitter, max_tries) -> (Linv, L, info) [autograd]
   gpk::variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter) -> (mean, var, flags, hyper)
                                                                                [autograd]
@@ -83,6 +84,19 @@ def exact_posterior(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor, Xs: Tensor) 
 def _(X, L, z, hyper, Xs):
     B, Ns, _ = Xs.shape
     return Xs.new_empty(B, Ns), Xs.new_empty(B, Ns)
+
+
+@torch.library.custom_op("gpk::exact_posterior_cov", mutates_args=(), device_types="cuda")
+def exact_posterior_cov(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor,
+                        Xs: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    p = ops.exact_posterior_cov(X, L, z, hyper, Xs)
+    return p.mean, p.var, p.cov
+
+
+@exact_posterior_cov.register_fake
+def _(X, L, z, hyper, Xs):
+    B, Ns, _ = Xs.shape
+    return Xs.new_empty(B, Ns), Xs.new_empty(B, Ns), Xs.new_empty(B, Ns, Ns)
 
 
 def _exact_setup(ctx, inputs, output):

@@ -171,6 +171,50 @@ def exact_posterior(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: to
     return ExactPosterior(mean, var)
 
 
+@dataclass
+class ExactPosteriorCov:
+    mean: torch.Tensor   # (B, Ns) posterior mean of f
+    var: torch.Tensor    # (B, Ns) posterior variance of f (unclamped) == diagonal(cov)
+    cov: torch.Tensor    # (B, Ns, Ns) posterior covariance of f, symmetric
+
+
+def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch.Tensor,
+                        Xs: torch.Tensor) -> ExactPosteriorCov:
+    """Joint exact-GP posterior at the test inputs ``Xs`` (B, Ns, D): ``exact_posterior``'s mean
+    and variance plus the dense covariance K(xs, xs) - V^T V, V = L^{-1} K* (two gfx950 kernel
+    launches of one C-ABI call, see include/gpk.h::gpk_exact_posterior_cov_f32). The V
+    workspace (B * N * Ns floats) lives only for the call."""
+    if X.dim() != 3 or Xs.dim() != 3:
+        raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
+    B, N, D = X.shape
+    if Xs.shape[0] != B or Xs.shape[2] != D:
+        raise ValueError(f"Xs must be (B, Ns, D) = ({B}, Ns, {D}), got {tuple(Xs.shape)}")
+    if L.shape != (B, N, N) or z.shape != (B, N):
+        raise ValueError("L / z do not match X")
+    _require_device(X, L, z, hyper, Xs)
+    X = X.detach().contiguous().float()
+    Xs = Xs.detach().contiguous().float()
+    L = L.detach().contiguous().float()
+    z = z.detach().contiguous().float()
+    Ns = Xs.shape[1]
+    dev = X.device
+    lib = _native.lib()
+    nbytes = lib.gpk_exact_posterior_cov_workspace_bytes(B, N, Ns)
+    if nbytes == 0 and B > 0 and Ns > 0:
+        raise ValueError(f"gpk_exact_posterior_cov_f32 does not support B={B}, N={N}, Ns={Ns}")
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    mean = torch.empty(B, Ns, device=dev, dtype=torch.float32)
+    var = torch.empty(B, Ns, device=dev, dtype=torch.float32)
+    cov = torch.empty(B, Ns, Ns, device=dev, dtype=torch.float32)
+    if B == 0 or Ns == 0:
+        return ExactPosteriorCov(mean, var, cov)
+    rc = lib.gpk_exact_posterior_cov_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), hyper.numel() - 3, Xs.data_ptr(),
+        B, N, Ns, D, ws.data_ptr(), mean.data_ptr(), var.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_exact_posterior_cov_f32")
+    return ExactPosteriorCov(mean, var, cov)
+
+
 INFO_TIMEOUT = 1 << 20   # gpk_exact.hip kInfoTimeout: a bounded LDS spin-wait expired
 
 

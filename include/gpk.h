@@ -110,6 +110,37 @@ int gpk_exact_posterior_f32(const float* X, const float* L, const float* z, cons
                             float* mean, float* var, void* stream);
 
 /*
+ * Joint exact-GP posterior at new inputs (eval mode), per window b: gpk_exact_posterior_f32
+ * plus the dense predictive covariance of the latent f, from the same training factor
+ * (nothing is refactored):
+ *   V    = L^{-1} K*                                  (K* as above; kept in the workspace)
+ *   mean = c + V^T z,   var = s2 - colsum(V o V)      (bitwise those of gpk_exact_posterior_f32)
+ *   cov  = K(xs, xs) - V^T V = K** - K*^T K_hat^{-1} K*,   K** = s2 * exp(-0.5 ||(xs_i - xs_j)/l||^2)
+ * cov is symmetric bit for bit and its diagonal is var bit for bit. Two phases on `stream`: the
+ * posterior kernel storing V, then one workgroup per 64 x 64 tile of the upper block triangle
+ * (K** by a centred fp32-MFMA Gram, V^T V on fp32 MFMA in a fixed order; every product exact
+ * fp32, no atomics: run-to-run deterministic).
+ *
+ * Replaces (reference): upstream exact_prediction_strategies.exact_predictive_covar (the full
+ * matrix, not only its diagonal), reached from ExactGPModel in eval mode
+ * (denoising_model/GPModel.py:10-13) through models/exact_gp.py __call__.
+ *
+ * Memory per call: the workspace, gpk_exact_posterior_cov_workspace_bytes(B, N, Ns) bytes
+ * (B * N * Ns floats of V, Ns rounded up to 64, and 64 B floats: the training mean of x / l
+ * that centres both Grams), plus the B * Ns^2 floats of cov.
+ * The query returns 0 for a shape the call does not accept.
+ *
+ * X, L, z, hyp, n_lengthscale, Xs, mean, var : as gpk_exact_posterior_f32 (N <= 800, D <= 64)
+ * workspace : device memory of the size above, 16-byte aligned
+ * cov : (B, Ns, Ns) float out, dense
+ * For N > 256 the blocked kernel keeps B on the grid's y dimension: B <= 65535 there (-7).
+ */
+size_t gpk_exact_posterior_cov_workspace_bytes(int B, int N, int Ns);
+int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
+                                void* workspace, float* mean, float* var, float* cov, void* stream);
+
+/*
  * Shared inducing-point factorisation of the whitened VariationalStrategy:
  *   A    = K_ZZ + jitter (fp32 add, as K_ZZ.add_jitter), then upcast to fp64
  *   L    = psd_safe_cholesky(A) with the fp64 ladder chol_jitter * 10^t
