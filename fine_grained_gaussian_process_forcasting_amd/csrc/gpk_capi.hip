@@ -8,7 +8,7 @@
 
 extern "C" {
 
-int gpk_version(void) { return 300; }
+int gpk_version(void) { return 400; }
 
 const char* gpk_strerror(int code) {
   if (code == 0) return "success";
@@ -485,6 +485,91 @@ int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const floa
   GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar,
                   (const float*)saved, O, shared_x ? 0LL : (long long)B * N * D};
   return gpk_launch_var_adjoint(a, (hipStream_t)stream);
+}
+
+// ---- dense covariance of q(f): phase 1 (A = Linv K_ZX, gpk_variational_cov.hip), then the
+//      variational mode of the covariance kernel (gpk_posterior_cov.hip)
+static bool var_cov_shape_ok(int B, int N, int M) {
+  if (B < 0 || N < 1 || M < 1 || M > 256) return false;
+  const long long T = ((long long)N + 63) / 64;
+  return (long long)B * (T * (T + 1) / 2) <= 0x7fffffffLL;   // one workgroup per tile on grid x
+}
+
+size_t gpk_variational_cov_workspace_bytes(int B, int N, int M) {
+  if (!var_cov_shape_ok(B, N, M)) return 0;
+  return gpk_var_cov_ws_floats(B, N, M) * sizeof(float);
+}
+
+size_t gpk_variational_cov_batched_workspace_bytes(int O, int B, int N, int M) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_variational_cov_workspace_bytes(B, N, M);
+}
+
+static int var_cov_run(const float* X, long long x_stride, const float* Z, const double* Linv,
+                       const float* vstd, const float* hyp, int O, int B, int N, int M, int D,
+                       void* workspace, float* cov, hipStream_t stream) {
+  GpkVarCovArgs a{hyp, X, (const float*)workspace, vstd, B, M, N, D, gpk_post_cov_vstride(N), cov, x_stride,
+                  (long long)gpk_var_cov_ws_floats(B, N, M)};
+  const int rc = gpk_launch_variational_cov_phase1(a, (float*)workspace, Z, Linv, O, stream);
+  if (rc != 0) return rc;
+  return gpk_launch_variational_cov_phase2(a, O, stream);
+}
+
+int gpk_variational_cov_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
+                            const float* hyp, int B, int N, int M, int D, void* workspace,
+                            float* cov, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vstd == nullptr) return -4;
+  if (hyp == nullptr) return -5;
+  if (B < 0) return -6;
+  if (N < 1) return -7;
+  if (M < 1 || M > 256) return -8;
+  if (D < 1 || D > 64) return -9;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -10;   // A rows are read 16 B at a time
+  if (cov == nullptr) return -11;
+  if (!var_cov_shape_ok(B, N, M)) return -7;
+  if (B == 0) return 0;
+  return var_cov_run(X, 0, Z, Linv, vstd, hyp, 1, B, N, M, D, workspace, cov, (hipStream_t)stream);
+}
+
+int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                    const float* vstd, const float* hyp, int O, int B, int N, int M,
+                                    int D, void* workspace, float* cov, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vstd == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (O < 1 || O > kGpkMaxOutputs) return -7;
+  if (B < 0) return -8;
+  if (N < 1) return -9;
+  if (M < 1 || M > 256) return -10;
+  if (D < 1 || D > 64) return -11;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
+  if (cov == nullptr) return -13;
+  if (!var_cov_shape_ok(B, N, M)) return -9;
+  if (B == 0) return 0;
+  return var_cov_run(X, shared_x ? 0LL : (long long)B * N * D, Z, Linv, vstd, hyp, O, B, N, M, D, workspace,
+                     cov, (hipStream_t)stream);
+}
+
+int gpk_mvn_root_max_n(void) { return kGpkMvnRootMaxN; }
+
+int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int B, int n, int S,
+                     float jitter, float* R, float* samples, int* info, void* stream) {
+  if (cov == nullptr) return -1;
+  if (S > 0 && mean == nullptr) return -2;
+  if (S > 0 && eps == nullptr) return -3;
+  if (B < 0) return -4;
+  if (n < 1 || n > kGpkMvnRootMaxN) return -5;
+  if (S < 0) return -6;
+  if (!(jitter >= 0.f)) return -7;
+  if (S > 0 && samples == nullptr) return -9;
+  if (info == nullptr) return -10;
+  if (B == 0) return 0;
+  return gpk_launch_mvn_root(cov, mean, eps, B, n, S, jitter, R, samples, info, (hipStream_t)stream);
 }
 
 int gpk_window_gather_f32(const float* table, long long n_rows, int F, const long long* rows, int B,

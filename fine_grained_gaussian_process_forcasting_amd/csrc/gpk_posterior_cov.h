@@ -39,3 +39,29 @@ struct GpkPostCovArgs {
   float* cov;          // (B, Ns, Ns) out
 };
 int gpk_launch_exact_posterior_cov(const GpkPostCovArgs& a, hipStream_t stream);
+
+// The same kernel's variational mode (gpk_variational_cov_f32): cov = K(x, x) + jitter I +
+// A^T diag(vstd^2 - 1) A, phase 1 in gpk_variational_cov.hip. Workspace per output (floats):
+// A = L^{-1} K_ZX row-major (B, M, as) with as = gpk_post_cov_vstride(N), then the window's
+// own mean of x / l (B, 64); ws_stride floats between two outputs' slices.
+struct GpkVarCovArgs {
+  const float* hyp;     // as GpkVarArgs (s2, jitter and the lengthscales are read)
+  const float* X;       // (B, N, D) inputs
+  const float* A;       // the workspace
+  const float* vstd;    // (M,)
+  int B, M, N, D, as;
+  float* cov;           // (B, N, N) out
+  long long x_stride;   // elements between two outputs' inputs (0: shared)
+  long long ws_stride;  // floats between two outputs' workspace slices
+};
+template <bool VAR>
+using GpkCovArgsOf = std::conditional_t<VAR, GpkVarCovArgs, GpkPostCovArgs>;
+size_t gpk_var_cov_ws_floats(int B, int N, int M);
+int gpk_launch_variational_cov_phase1(const GpkVarCovArgs& a, float* ws, const float* Z, const double* Linv,
+                                      int O, hipStream_t stream);
+int gpk_launch_variational_cov_phase2(const GpkVarCovArgs& a, int O, hipStream_t stream);
+
+// Batched Cholesky root of dense covariances fused with sampling (gpk_mvn_root.hip).
+constexpr int kGpkMvnRootMaxN = 256;
+int gpk_launch_mvn_root(const float* cov, const float* mean, const float* eps, int B, int n, int S,
+                        float jitter, float* R, float* samples, int* info, hipStream_t stream);

@@ -37,7 +37,14 @@ constexpr int kCovVS = kCovTile + 16; // LDS row stride of a V chunk: ds_read_b3
                                       // land 16 banks apart
 constexpr int kCovXS = 64 + 4;        // LDS row stride of the staged test inputs (as post_lds_layout)
 
-__global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
+// VAR = false: the exact posterior above. VAR = true: the covariance of a variational q(f),
+// cov = K(x, x) + jitter I + A^T diag(vstd^2 - 1) A from phase 1's A = L^{-1} K_ZX
+// (gpk_variational_cov.hip; workspace rows M, row stride as, then the window's own mean of
+// x / l): the weight vstd_m^2 - 1 is folded into the I-side panel as a chunk is staged, the
+// product is added, and the diagonal is computed here (K_ii = s2 exactly, + jitter). Output o
+// of a batched launch is blockIdx.y.
+template <bool VAR>
+__global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkCovArgsOf<VAR> a) {
   __shared__ float mu[64];
   __shared__ float lsc[64];
   __shared__ float nI[kCovTile];
@@ -50,7 +57,9 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
   float* vI = buf;
   float* vJ = buf + kCovKC * kCovVS;
 
-  const int N = a.N, Ns = a.Ns, D = a.D;
+  int N, Ns;
+  if constexpr (VAR) { N = a.M; Ns = a.N; } else { N = a.N; Ns = a.Ns; }
+  const int D = a.D;
   const int T = (Ns + kCovTile - 1) / kCovTile;
   const int P = T * (T + 1) / 2;
   // XCD-aware order: the tile pairs of one window go to the same XCD (shared L2 for V)
@@ -64,19 +73,39 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
   const int c = lane & 15, g = lane >> 4;
   const int D4 = (D + 3) & ~3;
 
-  const float s2 = a.hyp[0];
-  const float* Xs = a.Xs + (size_t)b * Ns * D;
-  const float* Vb = a.V + (size_t)b * N * a.vs;
+  const float* hyp = a.hyp;
+  const float* Xs;
+  const float* Vb;
+  const float* mup;
+  const float* wstd = nullptr;
+  int vs;
+  if constexpr (VAR) {
+    const size_t o = blockIdx.y;
+    hyp += o * (size_t)(4 + 2 * D);
+    Xs = a.X + o * (size_t)a.x_stride + (size_t)b * Ns * D;
+    Vb = a.A + o * (size_t)a.ws_stride + (size_t)b * N * a.as;
+    mup = a.A + o * (size_t)a.ws_stride + (size_t)a.B * N * a.as;
+    wstd = a.vstd + o * (size_t)N;
+    vs = a.as;
+  } else {
+    Xs = a.Xs + (size_t)b * Ns * D;
+    Vb = a.V + (size_t)b * N * a.vs;
+    mup = a.mu;
+    vs = a.vs;
+  }
+  const float s2 = hyp[0];
 
   // ---- the first V chunk's loads go out before anything else (one f32x4 per panel, thread
   //      and 16-row half chunk: row = 16 h + tid / 16, columns 4 (tid % 16) ..)
   const int vr = tid >> 4, vc = 4 * (tid & 15);
   f32x4 ra[2], rb[2];
+  float rw[2];
   auto vload = [&](int k0) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int row = k0 + 16 * h + vr;
-      const size_t off = (size_t)(row < N ? row : 0) * a.vs;
+      const size_t off = (size_t)(row < N ? row : 0) * vs;
+      if constexpr (VAR) rw[h] = wstd[row < N ? row : 0];
       ra[h] = *(const f32x4*)&Vb[off + kCovTile * ti + vc];
       rb[h] = *(const f32x4*)&Vb[off + kCovTile * tj + vc];
 #pragma unroll
@@ -90,8 +119,9 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
 
   // ---- phase 1's training mean of x / l, and the lengthscales
   if (tid < 64) {
-    mu[tid] = tid < D ? a.mu[(size_t)b * 64 + tid] : 0.f;
-    lsc[tid] = tid < D ? a.hyp[3 + (a.n_ls > 1 ? tid : 0)] : 1.f;
+    mu[tid] = tid < D ? mup[(size_t)b * 64 + tid] : 0.f;
+    if constexpr (VAR) lsc[tid] = tid < D ? hyp[4 + D + tid] : 1.f;
+    else lsc[tid] = tid < D ? hyp[3 + (a.n_ls > 1 ? tid : 0)] : 1.f;
   }
   lds_barrier();
   // ---- both sides' test inputs, scaled, centred, zero padded
@@ -146,7 +176,8 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
     lds_barrier();   // the previous chunk's reads are done
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      *(f32x4*)&vI[(16 * h + vr) * kCovVS + vc] = ra[h];
+      if constexpr (VAR) *(f32x4*)&vI[(16 * h + vr) * kCovVS + vc] = ra[h] * (rw[h] * rw[h] - 1.f);
+      else *(f32x4*)&vI[(16 * h + vr) * kCovVS + vc] = ra[h];
       *(f32x4*)&vJ[(16 * h + vr) * kCovVS + vc] = rb[h];
     }
     lds_barrier();
@@ -161,8 +192,13 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
   }
 
   // ---- Sigma tile and its mirror from the same registers; the diagonal is phase 1's var
+  //      (variational mode: s2 + jitter + the tile's own weighted sum of squares)
   float* Cb = a.cov + (size_t)b * Ns * Ns;
-  const float* varb = a.var + (size_t)b * Ns;
+  if constexpr (VAR) Cb += (size_t)blockIdx.y * a.B * Ns * Ns;
+  const float* varb = nullptr;
+  float dg = 0.f;
+  if constexpr (VAR) dg = s2 + hyp[2];
+  else varb = a.var + (size_t)b * Ns;
   const int col = kCovTile * tj + 16 * w + c;
 #pragma unroll
   for (int it = 0; it < 4; ++it)
@@ -171,11 +207,11 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkPostCovArgs a) {
       const int row = kCovTile * ti + 16 * it + 4 * g + r;
       if (row >= Ns || col >= Ns) continue;
       if (row < col) {
-        const float v = Kt[it][r] - acc[it][r];
+        const float v = VAR ? Kt[it][r] + acc[it][r] : Kt[it][r] - acc[it][r];
         Cb[(size_t)row * Ns + col] = v;
         Cb[(size_t)col * Ns + row] = v;
       } else if (row == col) {
-        Cb[(size_t)row * Ns + col] = varb[row];
+        Cb[(size_t)row * Ns + col] = VAR ? dg + acc[it][r] : varb[row];
       }
     }
 }
@@ -192,6 +228,14 @@ int gpk_launch_exact_posterior_cov(const GpkPostCovArgs& a, hipStream_t stream) 
   const long long T = (a.Ns + kCovTile - 1) / kCovTile;
   const long long grid = (long long)a.B * (T * (T + 1) / 2);
   if (grid > 0x7fffffff) return -7;
-  hipLaunchKernelGGL(gpk_post_cov_kernel, dim3((unsigned)grid), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(gpk_post_cov_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+int gpk_launch_variational_cov_phase2(const GpkVarCovArgs& a, int O, hipStream_t stream) {
+  const long long T = (a.N + kCovTile - 1) / kCovTile;
+  const long long grid = (long long)a.B * (T * (T + 1) / 2);
+  if (grid > 0x7fffffff) return -9;
+  hipLaunchKernelGGL(gpk_post_cov_kernel<true>, dim3((unsigned)grid, O), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }

@@ -293,14 +293,26 @@ class MultivariateNormal:
     def rsample(self, sample_shape=torch.Size(), base_samples: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Reparameterised sample mean + chol(Sigma) eps (upstream MultivariateNormal.rsample: the
         covariance root by psd_safe_cholesky with the jitter ladder). Off the hot path: the dense
-        covariance is materialised (covariance_matrix)."""
+        covariance is materialised (covariance_matrix). A CUDA fp32 distribution of n <= 256 points
+        through which no gradient can flow draws by gpk_mvn_root_f32 (factor and mean + R eps in one
+        launch, leading sample dimensions as S); every other case is torch arithmetic."""
         cov = self.covariance_matrix
-        root = psd_safe_cholesky(cov)
         shape = torch.Size(sample_shape) + self._mean.shape
         if base_samples is None:
             base_samples = torch.randn(shape, dtype=self._mean.dtype, device=self._mean.device)
         elif base_samples.shape != shape:
             raise RuntimeError(f"base_samples shape {tuple(base_samples.shape)} != {tuple(shape)}")
+        if (_mvn_root_eligible(cov) and self._mean.dtype == torch.float32 and base_samples.numel() > 0
+                and base_samples.is_cuda and base_samples.dtype == torch.float32
+                and _no_grad_flows(self._mean, base_samples)):
+            # eval-mode draw: the factor and mean + R eps in one launch (gpk_mvn_root_f32), the
+            # leading sample dimensions as its S; psd_safe_cholesky's ladder around it
+            n = self._mean.shape[-1]
+            nb = self._mean.numel() // n
+            _, smp = _mvn_root_ladder(cov.reshape(nb, n, n), None, self._mean.reshape(nb, n),
+                                      base_samples.reshape(-1, nb, n), want_R=False)
+            return smp.reshape(shape)
+        root = psd_safe_cholesky(cov)
         return self._mean + (root @ base_samples.unsqueeze(-1)).squeeze(-1)
 
     def sample(self, sample_shape=torch.Size(), base_samples: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -389,11 +401,65 @@ def rbf_covariance(X: torch.Tensor, lengthscale, outputscale) -> torch.Tensor:
     return s2 * torch.exp(-0.5 * d)
 
 
+def _no_grad_flows(*tensors) -> bool:
+    """No gradient can flow through an op on these tensors: grad mode is off, or none of them
+    requires grad."""
+    return not torch.is_grad_enabled() or not any(torch.is_tensor(t) and t.requires_grad for t in tensors)
+
+
+# Size rule of the HIP root: gpk_mvn_root_f32 keeps one matrix in one workgroup's LDS.
+MVN_ROOT_MAX_N = ops.MVN_ROOT_MAX_N
+
+
+def _mvn_root_eligible(A: torch.Tensor) -> bool:
+    """A dense covariance (batch) the HIP Cholesky root takes: CUDA, fp32, 1 <= n <= 256, and no
+    gradient needed through it."""
+    return (torch.is_tensor(A) and A.is_cuda and A.dtype == torch.float32 and A.dim() >= 2
+            and A.shape[-1] == A.shape[-2] and 1 <= A.shape[-1] <= MVN_ROOT_MAX_N and _no_grad_flows(A))
+
+
+def _mvn_root_ladder(A: torch.Tensor, max_tries: Optional[int], mean: Optional[torch.Tensor] = None,
+                     eps: Optional[torch.Tensor] = None, want_R: bool = True):
+    """psd_safe_cholesky's sequence on gpk::mvn_root for A (B, n, n): jitter 0; on any failure
+    the NaN check (NanError), then up to max_tries relaunches of the WHOLE batch with
+    cholesky_jitter * 10^t (upstream adds the jitter to every matrix of the batch), each warning
+    NumericalWarning; NotPSDError after the last. Returns (R or None, samples or None)."""
+    def launch(jit):
+        R, smp, info = torch.ops.gpk.mvn_root(A, float(jit), mean, eps, want_R)
+        ok = not bool((info > 0).any())
+        return ok, (R if want_R else None), (smp if eps is not None else None)
+
+    ok, R, smp = launch(0.0)
+    if ok:
+        return R, smp
+    if torch.isnan(A).any():
+        from .errors import NanError
+        raise NanError(f"cholesky_cpu: {torch.isnan(A).sum().item()} of {A.numel()} elements of the "
+                       f"{tuple(A.shape)} tensor are NaN.")
+    jitter = settings.cholesky_jitter.value(A.dtype)
+    tries = settings.cholesky_max_tries.value() if max_tries is None else max_tries
+    jitter_new = 0.0
+    for i in range(tries):
+        jitter_new = jitter * (10 ** i)
+        warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
+        ok, R, smp = launch(jitter_new)
+        if ok:
+            return R, smp
+    from .errors import NotPSDError
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
+
+
 def psd_safe_cholesky(A: torch.Tensor, max_tries: Optional[int] = None) -> torch.Tensor:
     """Upstream linear_operator utils/cholesky.py psd_safe_cholesky for a dense matrix (the
     covariance roots of rsample; the hot path's factorisations run in the gfx950 kernels):
     torch.linalg.cholesky_ex, then up to max_tries retries with jitter 1e-6, 1e-5, ... (fp32;
-    1e-8.. for fp64) added to the diagonal, each retry warning NumericalWarning."""
+    1e-8.. for fp64) added to the diagonal, each retry warning NumericalWarning. A CUDA fp32
+    matrix of n <= 256 that needs no gradient runs the same ladder on gpk_mvn_root_f32 (each
+    rung one launch over the whole batch); everything else takes the torch path."""
+    if _mvn_root_eligible(A) and A.numel() > 0:
+        n = A.shape[-1]
+        R, _ = _mvn_root_ladder(A.reshape(-1, n, n), max_tries)
+        return R.reshape(A.shape)
     L, info = torch.linalg.cholesky_ex(A)
     if not bool((info > 0).any()):
         return L
@@ -589,6 +655,14 @@ def variational_dense_covariance(x, Z, Linv, vstd, outputscale, lengthscale, jit
     return Kxx + jitter * eye + A.transpose(-1, -2) @ (mid[:, None] * A)
 
 
+def _variational_cov_on_kernels(x, Z, Linv, vstd, outputscale, lengthscale) -> bool:
+    """The dense covariance of q(f) runs on gpk_variational_cov_f32 when no gradient can flow
+    (grad mode off, or none of the tensors requires grad) and the inputs are CUDA fp32; the
+    differentiable covariance and every CPU path stay the dense torch restatement."""
+    return (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32 and x.numel() > 0
+            and _no_grad_flows(x, Z, Linv, vstd, outputscale, lengthscale))
+
+
 class VariationalStrategy(nn.Module):
     """Whitened VariationalStrategy for one DeepGP layer (output_dims=None).
 
@@ -659,11 +733,13 @@ class VariationalStrategy(nn.Module):
         """q(f) of one output on the kernels + a lazy dense covariance for covariance_matrix /
         rsample (upstream VariationalStrategy.forward's predictive_covar)."""
         from .ops_autograd import variational_predict
-        mean, var, flag, Linv = variational_predict(
+        mean, var, flag, Linv, hyper = variational_predict(
             xf, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter, cache=cache,
-            key_tensors=key, return_linv=True)
+            key_tensors=key, return_linv=True, return_hyper=True)
 
         def cov():
+            if _variational_cov_on_kernels(xf, Z, Linv, vstd, outputscale, lengthscale):
+                return torch.ops.gpk.variational_cov(xf, Linv, Z, vstd, hyper)
             return variational_dense_covariance(xf, Z, Linv, vstd, outputscale, lengthscale, jitter)
         return mean, var, flag, cov
 
@@ -674,7 +750,9 @@ class VariationalStrategy(nn.Module):
         (ops_autograd.variational_predict_batched): the O K_ZZ factors are one cache entry, the
         expanded inputs are read in place by every output (no (O, B, N, D) copy), and the
         per-output dLinv flow into one batched K_ZZ adjoint. Returns the batch (..., O) of
-        per-output q(f); the covariance stays dense torch arithmetic from Linv[o] on request."""
+        per-output q(f); the covariance is materialised on request, by the kernels
+        (gpk::variational_cov, all outputs on one launch chain) when no gradient can flow, else
+        as dense torch arithmetic from Linv[o]."""
         from .ops_autograd import variational_predict_batched
         Z = self.inducing_points
         O, M, D = Z.shape
@@ -695,11 +773,14 @@ class VariationalStrategy(nn.Module):
             xk = x[..., 0, :, :].reshape(-1, N, D)
         else:
             xk = x.movedim(-3, 0).reshape(O, -1, N, D)
-        mean, var, flag, Linv = variational_predict_batched(
+        mean, var, flag, Linv, hyper = variational_predict_batched(
             xk, Z, vm, vs, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
-            return_linv=True)
+            return_linv=True, return_hyper=True)
 
         def cov():
+            if _variational_cov_on_kernels(xk, Z, Linv, vs, s2, ls):
+                c = torch.ops.gpk.variational_cov(xk, Linv, Z, vs, hyper)       # (O, B', N, N)
+                return c.reshape(O, *batch, N, N).movedim(0, -3)
             xo = xk.expand(O, *xk.shape) if xk.dim() == 3 else xk
             return torch.stack([variational_dense_covariance(xo[o], Z[o], Linv[o], vs[o], s2[o], ls[o], jitter)
                                 .reshape(*batch, N, N) for o in range(O)], dim=-3)

@@ -21,6 +21,8 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::meanfield_kl(m, s) -> kl (1,)                                          [autograd]
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
                                                                                [autograd]
+  gpk::variational_cov(x, Linv, Z, vstd, hyper) -> cov                        [eval only]
+  gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [eval only]
 
 Reference call sites they serve: GPModel.py:10-13 + ExactMarginalLogLikelihood
 (exact_mll), ExactGPModel in eval mode (exact_posterior), DeepGP.py:33-73 VariationalStrategy (kzz_factor, variational_fwd),
@@ -29,7 +31,7 @@ train.py:166 (the *_grad / *_adj ops).
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -495,3 +497,43 @@ def _elbo_backward(ctx, gelbo, _gflag):
 
 
 variational_elbo.register_autograd(_elbo_backward, setup_context=_elbo_setup)
+
+# ---------------------------------------------------------------------------
+# eval-mode draws: dense covariance of q(f) (gpk_variational_cov_f32) and the batched Cholesky
+# root fused with sampling (gpk_mvn_root_f32). No autograd formula: gp.py calls them only when
+# no gradient can flow and keeps the dense torch restatement for every other case.
+# ---------------------------------------------------------------------------
+
+
+@torch.library.custom_op("gpk::variational_cov", mutates_args=(), device_types="cuda")
+def variational_cov(x: Tensor, Linv: Tensor, Z: Tensor, vstd: Tensor, hyper: Tensor) -> Tensor:
+    """Z (M, D): x (B, N, D) -> cov (B, N, N). Z (O, M, D), the outputs of a multi-output
+    layer on one launch chain: x (B, N, D) shared or (O, B, N, D) -> cov (O, B, N, N)."""
+    if Z.dim() == 3:
+        return ops.variational_cov_batched(x, Z, Linv, vstd, hyper)
+    return ops.variational_cov(x, Z, Linv, vstd, hyper)
+
+
+@variational_cov.register_fake
+def _(x, Linv, Z, vstd, hyper):
+    B, N = x.shape[-3], x.shape[-2]
+    if Z.dim() == 3:
+        return x.new_empty(Z.shape[0], B, N, N)
+    return x.new_empty(B, N, N)
+
+
+@torch.library.custom_op("gpk::mvn_root", mutates_args=(), device_types="cuda")
+def mvn_root(cov: Tensor, jitter: float, mean: Optional[Tensor] = None, eps: Optional[Tensor] = None,
+             want_R: bool = True) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (R (B, n, n) or empty, samples (S, B, n) or empty, info (B,) int32)."""
+    R, samples, info = ops.mvn_root(cov, jitter, mean, eps, want_R)
+    return (R if R is not None else cov.new_empty(0), samples if samples is not None else cov.new_empty(0),
+            info)
+
+
+@mvn_root.register_fake
+def _(cov, jitter, mean=None, eps=None, want_R=True):
+    B, n, _ = cov.shape
+    return (cov.new_empty(B, n, n) if want_R else cov.new_empty(0),
+            cov.new_empty(eps.shape[0], B, n) if eps is not None else cov.new_empty(0),
+            cov.new_empty(B, dtype=torch.int32))

@@ -737,6 +737,130 @@ def variational_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Te
     return VariationalOut(mean, var, None, flags, saved)
 
 
+def variational_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
+                    hyper: torch.Tensor) -> torch.Tensor:
+    """Dense covariance of q(f) at X (B, N, D): K_XX + jitter I + A^T diag(vstd^2 - 1) A with
+    A = Linv K_ZX (two gfx950 kernel launches of one C-ABI call, see
+    include/gpk.h::gpk_variational_cov_f32). ``hyper`` is the variational path's packed device
+    vector (pack_variational_hyper). Memory per call: the A workspace (B * M * N floats, N
+    rounded up to 64, + 64 B) lives only for the call; the result is B * N^2 floats."""
+    if X.dim() != 3:
+        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
+    B, N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape != (M, D):
+        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
+    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
+    if hyper.numel() != 4 + 2 * D:
+        raise ValueError(f"hyper must have 4 + 2D = {4 + 2 * D} entries, got {hyper.numel()}")
+    _require_device(X, Z, Linv, vstd, hyper)
+    dev = X.device
+    X = X.detach().contiguous().float()
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vstd = vstd.detach().contiguous().float().reshape(-1)
+    hyper = hyper.detach().contiguous().float()
+    if vstd.numel() != M:
+        raise ValueError(f"vstd must have M = {M} entries, got {vstd.numel()}")
+    lib = _native.lib()
+    nbytes = lib.gpk_variational_cov_workspace_bytes(B, N, M)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_variational_cov_f32 does not support B={B}, N={N}, M={M}")
+    cov = torch.empty(B, N, N, device=dev, dtype=torch.float32)
+    if B == 0:
+        return cov
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_cov_f32(X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(),
+                                     hyper.data_ptr(), B, N, M, D, ws.data_ptr(), cov.data_ptr(),
+                                     _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_cov_f32")
+    return cov
+
+
+def variational_cov_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
+                            hyper: torch.Tensor) -> torch.Tensor:
+    """``variational_cov`` for O outputs in one launch chain (gpk_variational_cov_batched_f32): X
+    (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64, vstd
+    (O, M), hyper (O, 4 + 2D) -> cov (O, B, N, N). Bit-identical to O single-output calls.
+    Memory per call: O workspaces of ``variational_cov`` + the O * B * N^2 floats of cov."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    _require_device(X, Z, Linv, vstd, hyper)
+    X, shared = _batched_x(X, O)
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
+    if tuple(hyper.shape) != (O, 4 + 2 * D):
+        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+    dev = X.device
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vstd = vstd.detach().reshape(O, M).contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    lib = _native.lib()
+    nbytes = lib.gpk_variational_cov_batched_workspace_bytes(O, B, N, M)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_variational_cov_batched_f32 does not support O={O}, B={B}, N={N}, M={M}")
+    cov = torch.empty(O, B, N, N, device=dev, dtype=torch.float32)
+    if B == 0:
+        return cov
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_cov_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), O, B,
+        N, M, D, ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_cov_batched_f32")
+    return cov
+
+
+MVN_ROOT_MAX_N = 256   # gpk_mvn_root_max_n(): the matrix lives in one workgroup's LDS
+
+
+def mvn_root(cov: torch.Tensor, jitter: float = 0.0, mean: Optional[torch.Tensor] = None,
+             eps: Optional[torch.Tensor] = None, want_R: bool = True):
+    """Lower Cholesky factor R of cov + jitter I for a batch (B, n, n) of dense covariances and,
+    with ``mean`` (B, n) and ``eps`` (S, B, n), the draws mean + R eps, in ONE gfx950 launch
+    (include/gpk.h::gpk_mvn_root_f32; n <= 256). Returns (R or None, samples (S, B, n) or None,
+    info (B,) int32); info[b] > 0: matrix b is not positive definite at this jitter, R[b] and
+    its samples must not be read. One rung of psd_safe_cholesky's ladder: the caller retries the
+    whole batch. Memory per call: only the outputs (B * n^2 floats of R when asked, S * B * n of
+    samples); the matrix is factored in LDS."""
+    if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2]:
+        raise ValueError(f"cov must be (B, n, n), got {tuple(cov.shape)}")
+    B, n, _ = cov.shape
+    if not 1 <= n <= MVN_ROOT_MAX_N:
+        raise ValueError(f"gpk_mvn_root_f32 takes 1 <= n <= {MVN_ROOT_MAX_N}, got n = {n}")
+    if (mean is None) != (eps is None):
+        raise ValueError("mean and eps are given together")
+    _require_device(cov)
+    dev = cov.device
+    cov = cov.detach().contiguous().float()
+    S = 0
+    samples = None
+    if eps is not None:
+        _require_device(mean, eps)
+        if eps.dim() != 3 or tuple(eps.shape[1:]) != (B, n) or tuple(mean.shape) != (B, n):
+            raise ValueError(f"mean must be (B, n) = {(B, n)} and eps (S, B, n); got {tuple(mean.shape)}, "
+                             f"{tuple(eps.shape)}")
+        S = eps.shape[0]
+        mean = mean.detach().contiguous().float()
+        eps = eps.detach().contiguous().float()
+        samples = torch.empty(S, B, n, device=dev, dtype=torch.float32)
+    R = torch.empty(B, n, n, device=dev, dtype=torch.float32) if want_R else None
+    info = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return R, samples, info
+    rc = _native.lib().gpk_mvn_root_f32(
+        cov.data_ptr(), mean.data_ptr() if S > 0 else None, eps.data_ptr() if S > 0 else None, B, n, S,
+        float(jitter), R.data_ptr() if R is not None else None,
+        samples.data_ptr() if S > 0 else None, info.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_mvn_root_f32")
+    return R, samples, info
+
+
 @dataclass
 class VariationalAdjointBatched:
     dX: torch.Tensor      # (O, B, N, D) per output (shared inputs: the caller sums over O)

@@ -134,10 +134,12 @@ def _mean_params(mean_module, D, device):
 
 
 def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
-                        cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
+                        cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False,
+                        return_hyper: bool = False):
     """q(f) mean / variance / clamp flag for (B, N, D) windows (HIP forward and backward;
     see module docstring). ``cache`` shares the K_ZZ factor between calls; ``return_linv``
-    appends the factor's L^{-1} (for a lazily materialised covariance)."""
+    appends the factor's L^{-1} (for a lazily materialised covariance), ``return_hyper`` the
+    packed hyper vector of the forward (what gpk::variational_cov reads)."""
     w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
     s2 = outputscale.reshape(())
     ls = lengthscale.reshape(-1)
@@ -149,13 +151,16 @@ def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module
     Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
     # training (a gradient will flow): the forward keeps A for the saved-state adjoint
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
-    mean, var, flags, _, _ = torch.ops.gpk.variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
-                                                           float(jitter), save)
+    mean, var, flags, hyper, _ = torch.ops.gpk.variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
+                                                               float(jitter), save)
     cache.note_consumers(mean, var)
     cache.check_pending()
+    out = (mean, var, flags)
     if return_linv:
-        return mean, var, flags, Linv
-    return mean, var, flags
+        out += (Linv,)
+    if return_hyper:
+        out += (hyper,)
+    return out
 
 
 def _mean_params_batched(mean_module, O, D, device):
@@ -178,7 +183,8 @@ def _mean_params_batched(mean_module, O, D, device):
 
 
 def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
-                                cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
+                                cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False,
+                                return_hyper: bool = False):
     """``variational_predict`` for the O independent output GPs of a multi-output layer, one
     launch chain each way: x (B, N, D) shared by the outputs or (O, B, N, D), Z (O, M, D), vmean /
     vstd (O, M), outputscale (O,), lengthscale (O, D) -> mean, var (O, B, N), one clamp flag for
@@ -196,10 +202,13 @@ def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mea
         key_tensors = (Z, s2, ls)
     Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
     save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
-    mean, var, flags, _, _ = torch.ops.gpk.variational_fwd_batched(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
-                                                                   float(jitter), save)
+    mean, var, flags, hyper, _ = torch.ops.gpk.variational_fwd_batched(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
+                                                                       float(jitter), save)
     cache.note_consumers(mean, var)
     cache.check_pending()
+    out = (mean, var, flags)
     if return_linv:
-        return mean, var, flags, Linv
-    return mean, var, flags
+        out += (Linv,)
+    if return_hyper:
+        out += (hyper,)
+    return out

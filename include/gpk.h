@@ -401,6 +401,75 @@ int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const floa
                                         double* dLinv, float* dZ, float* dpar, void* stream);
 
 /*
+ * Dense predictive covariance of the variational q(f) (eval mode), per window b, from the
+ * shared K_ZZ factor of gpk_kzz_chol_f64:
+ *   K_ZX = s2 * exp(-0.5 ||(z_m - x_i)/l||^2)        (fp32, the arithmetic of gpk_variational_f32)
+ *   A    = Linv K_ZX                                  (fp64 MFMA, cast to fp32; kept in the workspace)
+ *   cov  = K_XX + jitter I + A^T diag(vstd^2 - 1) A   (N x N)
+ *   K_XX = s2 * exp(-0.5 d2) with upstream _sq_dist semantics for x1 == x2: inputs / l centred
+ *          by the window's mean, d2 clamped at 0, diagonal exactly 0 (K_ii = s2)
+ * The diagonal is the unclamped variance s2 + jitter + sum_m A_mi^2 (vstd_m^2 - 1). cov is
+ * symmetric bit for bit. Two phases on `stream`: one workgroup per (window, 64-point column
+ * block) storing A and the window's mean of x / l, then one workgroup per 64 x 64 tile of the
+ * upper block triangle (the variational mode of the exact posterior's covariance kernel: the
+ * weight vstd_m^2 - 1 folded into one operand, fp32 MFMA in a fixed order, no atomics:
+ * run-to-run deterministic).
+ *
+ * Replaces (reference): upstream variational/variational_strategy.py forward's
+ * predictive_covar (SumLinearOperator(data_data_covar.add_jitter, MatmulLinearOperator(...)))
+ * evaluated densely, as MultivariateNormal.rsample / covariance_matrix of a DeepGP layer
+ * output do (denoising_model/DeepGP.py:62-64 ``x.rsample()`` of a layer fed with a skip input).
+ *
+ * Memory per call: the workspace, gpk_variational_cov_workspace_bytes(B, N, M) bytes (B * M * N
+ * floats of A, N rounded up to 64, and 64 B floats of means), plus the B * N^2 floats of cov.
+ * The query returns 0 for a shape the call does not accept.
+ *
+ * X : (B, N, D) float   Z : (M, D) float   Linv : (M, M) double   vstd : (M,) float
+ * hyp : as gpk_variational_f32 {s2, noise, jitter, bias, weights[D], lengthscale[D]}; noise,
+ *       bias and weights are not read
+ * M <= 256, D <= 64, N >= 1, B >= 0   workspace : device memory of the size above, 16-byte aligned
+ * cov : (B, N, N) float out, dense
+ *
+ * The batched call runs O outputs (independent GPs of a multi-output layer) with o on a grid
+ * dimension: leading dense O on Z, Linv, vstd, hyp and cov; X (B, N, D) read by every output
+ * (shared_x != 0) or (O, B, N, D); the workspace is O slices of the single-output query.
+ * Output o is bit-identical to a single-output call on output o's arrays.
+ */
+size_t gpk_variational_cov_workspace_bytes(int B, int N, int M);
+int gpk_variational_cov_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
+                            const float* hyp, int B, int N, int M, int D, void* workspace,
+                            float* cov, void* stream);
+size_t gpk_variational_cov_batched_workspace_bytes(int O, int B, int N, int M);
+int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                    const float* vstd, const float* hyp, int O, int B, int N, int M,
+                                    int D, void* workspace, float* cov, void* stream);
+
+/*
+ * Batched Cholesky root of dense covariances, fused with sampling: per matrix b
+ *   R R^T = cov[b] + jitter I        (lower factor, fp32, one workgroup, the matrix in LDS)
+ *   samples[s, b, i] = mean[b, i] + sum_{j <= i} R[b, i, j] eps[s, b, j]   (ascending j)
+ * One rung of psd_safe_cholesky's ladder: there is no retry inside the kernel, the caller
+ * relaunches the whole batch with jitter * 10^t, as upstream adds the jitter to every matrix
+ * of a batch when one fails.
+ *
+ * Replaces (reference): upstream linear_operator utils/cholesky.py psd_safe_cholesky's
+ * torch.linalg.cholesky_ex and distributions/multivariate_normal.py rsample's root matmul
+ * (denoising_model/DeepGP.py:62-64 ``x.rsample()``; DeepGPp.predict(x)[1].rsample() in eval).
+ *
+ * cov : (B, n, n) float, dense; only the lower triangle is read   jitter : added to the
+ *       diagonal in fp32 on load
+ * R : (B, n, n) float out or NULL; lower factor, upper triangle zero
+ * mean : (B, n)   eps : (S, B, n)   samples : (S, B, n) out. S = 0 with NULL eps / mean /
+ *       samples gives the factor only; S > 0 needs all three
+ * info : (B,) int out. 0 = factored; k > 0 = the pivot of column k (1-based) was not positive
+ *       or was NaN: R[b] and the samples of b are then unspecified and must not be read
+ * 1 <= n <= gpk_mvn_root_max_n() = 256, B >= 0. Deterministic (fixed order, no atomics).
+ */
+int gpk_mvn_root_max_n(void);
+int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int B, int n, int S,
+                     float jitter, float* R, float* samples, int* info, void* stream);
+
+/*
  * GPU-resident training-window gather:
  *   for window b with first row r = rows[b] of the (id, time)-sorted table:
  *     enc[b] = table[r      : r + n_enc]                  (n_enc, F)
