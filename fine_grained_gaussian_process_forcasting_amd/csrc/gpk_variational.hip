@@ -9,7 +9,23 @@
 //     var  = s2 + jitter + sum_m A_mi^2 (s_m^2 - 1), clamped >= 1e-6 (MVN.variance)
 //     ELL  = sum_i -0.5 [((y_i - mean_i)^2 + var_i)/noise + log noise + log 2pi]
 //
-// Kernels (the shared K_ZZ factor and its adjoint: gpk_kzz.hip, gpk_kzz_grad.hip):
+// (the shared K_ZZ factor and its adjoint: gpk_kzz.hip, gpk_kzz_grad.hip)
+//
+// Three kernel families and a shared tail live in this file; which shape goes where (M inducing
+// points, D input dims; gpk_launch_var / launch_var_adj below, the first match):
+//   M <= 64, D <= 32 (GPK_VAR_REG)   register-resident path: gpk_var_fwd_r_kernel,
+//                                    gpk_var_adj_r_kernel (K-Gram folded in), RegLds
+//   M > 64 (GPK_VAR_LREG)            L^{-1}-in-registers path: gpk_var_fwd_l_kernel (training keeps
+//                                    A where the saved-state adjoint serves, LSaved); adjoint with
+//                                    that state: gpk_var_adjs_l_kernel + gpk_var_kgram_l_kernel;
+//                                    without: gpk_var_adja_l_kernel + gpk_var_adjk_l_kernel, if their
+//                                    LDS plan fits and the dA / K_ZX workspace stays under 2 GB
+//   everything else                  LDS-tiled path (today only the fallback): M <= 64 with D in
+//                                    (32, 64], and the M > 64 adjoints left over by the line above
+//   every path                       gpk_var_ell_kernel after a forward; gpk_dlinv_kernel (paths
+//                                    with a dA / K_ZX workspace), gpk_var_red_kernel and
+//                                    gpk_var_fin_kernel after an adjoint
+// The LDS-tiled kernels and the tail:
 //   gpk_var_fwd_kernel  the per-point work as ONE column-tiled GEMM A = L^{-1} [K_ZX(b=0) | ...]:
 //                       a workgroup owns a chunk of TW points of one window and all M rows of A;
 //                       K_ZX chunk from an f32-MFMA Gram (GPyTorch's centred _sq_dist form) in
