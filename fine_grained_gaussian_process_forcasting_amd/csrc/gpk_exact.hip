@@ -32,6 +32,10 @@
 // readlane-broadcast instruction stream.
 // Flag waits read LDS only (ds_read + lgkmcnt): the L stores stream out behind
 // the factorisation instead of being drained at each step.
+// In the column-ownership plan (N in 241..256 at two windows per CU, worker_step_col)
+// the right-hand side is not a tile at all: each of its block rows is 16 floats in
+// LDS, updated by the wave that owns that block column with a VALU matvec straight
+// from the TRSM's result registers, and z_k travels as 16 unrounded fp32 words.
 #include "gpk_common.h"
 #include "gpk_internal.h"
 
@@ -342,6 +346,11 @@ GPK_DEVICE void spin_until(lds_vint* flags, int idx, int target) {
 // check, and none waits for work that never comes. A new wait must keep this invariant: wait
 // only for work of steps <= K that precedes the producer's next check (else it spins until
 // the 2^18-poll bound).
+// The column plan's z wait (phase 4c: z_K inside step K) keeps it: the owner of column K
+// publishes z_K right after it has passed its step-K check and the kFlagBulk wait, before its
+// own TRSM and long before its step-(K+1) check. What it waits on there is step K-1 work of
+// every wave (the bulk count, behind that wave's wait for z_{K-1}: by induction over K no
+// wave waiting for z_K is waited on), never anything of a wave that is waiting for z_K.
 #define GPK_WAITF(idx, target)                                                  \
   {                                                                             \
     unsigned long long _w0 = 0;                                                 \
@@ -359,6 +368,9 @@ GPK_DEVICE void spin_until(lds_vint* flags, int idx, int target) {
 // consumer compares it after the acquire.
 constexpr int kFlagEpochBad = 84;   // site | slot << 8 of the first mismatch (check builds)
 constexpr int kShadowPan = 96, kShadowHo = 130, kShadowW = 134;
+// (column plan) the z vector of the latest step: one word, since z_{k+1} is published only after
+// every wave has counted in on kFlagBulk for step k, i.e. after its read of z_k
+constexpr int kShadowZ = 137;
 GPK_DEVICE void epoch_mark(lds_vint* flags, int idx, int epoch, int lane) {
   if (lane == 0) flags[idx] = epoch;
 }
@@ -951,16 +963,26 @@ GPK_DEVICE int worker_step_split(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
 // through per-column panel flags (kFlagPan + j), the z flag and two monotone counters
 // (TRSM phases done / panel reads done) instead of a workgroup-wide step barrier:
 //   2. the other tiles of block row K through panel K-1 (this step's TRSM inputs);
-//   3. right-hand side row K (owner of column K);
-//   4. TRSM of row K with R_KK^{-T} (+ z_K): panel K, flags; the panel buffer is reused
-//      only once every wave has finished reading panel K-2 (kFlagBulk);
+//   3. once R_KK^{-T} is out and every wave has finished reading panel K-2 (kFlagBulk): z_K
+//      by the owner of column K, as 16 fp32 words (kFlagZ); then the TRSM of row K: panel K,
+//      flags, kFlagTrsm count;
 //   4b. the NEXT step's hand-over HO_{K+1} = (K+1, K+2), (K+2, K+2), by their owners: panel
-//      K-1, (K+2, K+2)'s deferred RBF, then panel K as soon as R_{K,K+1}, R_{K,K+2} are out
+//      K-1, (K+2, K+2)'s deferred RBF, then panel K as soon as R_{K,K+1} is out (R_{K,K+2} is
+//      the owner's own tile: read back from the panel without a wait on the own flag)
 //      (round 5; before, HO_K opened step K, i.e. it waited for the owners' whole step K-1);
+//   4c. right-hand side: rw_j += R_{K,j}^T z_K for the owned columns, on the VALU from the
+//      TRSM's result registers (hand-over owners: after 4b, from the panel);
 //   5. the rest of the trailing update through panel K-1 once panel K-1 is complete
-//      (kFlagTrsm), one P load per column;
-//   6. right-hand side rows > K of the owned columns; count the panel reads done;
-//   7. deferred RBF of block row K+2 (less (K+2, K+2): 4b), zero-L.
+//      (kFlagTrsm), one P load per column; count the panel reads done (kFlagBulk);
+//   6. deferred RBF of block row K+2 (less (K+2, K+2): 4b), zero-L.
+// The right-hand side y - c never becomes a tile here. The rw area is 16 slots of 16 floats:
+// slot j holds rw_j, the running -(y - c) of block row j, until step j solves it into z_j in
+// place (so no z is overwritten within an attempt). Slot j is updated only by the wave that
+// produces R_{K,j} -- the owner of column j, in program order -- by a 16-lane read-add-write
+// whose read goes out together with the z_K read. Column 8's tiles come from wave K (K <= 6)
+// and wave 0 (K = 7): one producer per step, ordered from step to step by kFlagBulk, so the
+// sum order is fixed (bit-deterministic, no atomics). Keeping the rows in one VGPR per owned
+// column instead was tried first: 128 VGPRs with 1 (N = 256) / 80 (padded) spilled registers.
 // ---------------------------------------------------------------------------
 constexpr int kColSlots = 20;
 
@@ -983,6 +1005,17 @@ GPK_DEVICE f32x4 pan_mma2(const pan_op_t q, const pan_op_t p_hl, const pan_op_t 
 GPK_DEVICE pan_op_t pan_swap(const pan_op_t p) {
 #if GPK_SPLIT_UPDATE
   return pan_op_t{p[4], p[5], p[6], p[7], p[0], p[1], p[2], p[3]};
+#else
+  return p;
+#endif
+}
+
+GPK_DEVICE f32x4 pan_f32(const pan_op_t p) {   // the tile's values (what pan_store returned)
+#if GPK_SPLIT_UPDATE
+  f32x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = (float)p[r] + (float)p[4 + r];
+  return o;
 #else
   return p;
 #endif
@@ -1047,21 +1080,8 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
       }
     }
   }
-  // ---- 3. right-hand side row K: rw_K += R_{K-1,K}^T z_{K-1} (owner of column K)
-  if constexpr (K > 0) {
-    if (wv == OWN_K) {
-      GPK_WAITF(kFlagZ, e0 + K - 1)
-      if constexpr (K == 8) { GPK_WAITF(kFlagPan + 8, e0 + K - 1) }
-      f32x4 d = *(const f32x4*)&x.rw[16 * K + 4 * grp];
-      if (c != 0) d = f32x4{0.f, 0.f, 0.f, 0.f};
-      GPK_EP(pck(pprev + K * 256, 14);)
-      GPK_EP(pck(pprev + NB * 256, 14);)
-      d = pan_mma(pan_load(pprev + K * 256, lane), pprev + NB * 256, lane, d);
-      if (c == 0) *(f32x4*)&x.rw[16 * K + 4 * grp] = d;
-    }
-  }
-  GPK_WSTAMP(6, 2)  // row K + RHS row K
-  // ---- 4. TRSM of row K with R_KK^{-T} (panel K) and z_K
+  GPK_WSTAMP(6, 2)  // row K
+  // ---- 3. z_K, then the TRSM of row K with R_KK^{-T} (panel K)
   const float* wbk = x.wbuf + (K % 3) * kWBuf;
   const int flag_now = x.vflag[kFlagFact];
   int fail = x.vflag[kFlagFail + e0 / 32];
@@ -1079,36 +1099,18 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
   // panel buffer K & 1 held panel K-2 (read in step K-1): every wave must be past step K-1's
   // panel reads (one kFlagBulk add per wave per step)
   if constexpr (K >= 2) { GPK_WAITF(kFlagBulk, WK * K) }
-  {
-    const WOp wq = w_split(q);
-    const bool a_t = (K + 1 <= jA), b_t = (K + 1 <= jB);
-    if (a_t) {
-      const f32x4 r = pan_store(pcur + jA * 256, lane, trsm_tile(wq, acc[K]));
-      GPK_EP(epoch_pan_mark(x, pcur + jA * 256, e0 + K + ((kEpochSabotage && K == 3) ? 1 : 0));)
-      if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * jA + c, 16 * K + 4 * grp, r * inv_sigma);
-    }
-    if constexpr (17 - K >= 0 && 17 - K < 18) {
-      if (b_t) {
-        const f32x4 r = pan_store(pcur + jB * 256, lane, trsm_tile(wq, acc[17 - K]));
-        GPK_EP(epoch_pan_mark(x, pcur + jB * 256, e0 + K);)
-        if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * jB + c, 16 * K + 4 * grp, r * inv_sigma);
-      }
-    }
-    constexpr int C8S = K <= 6 ? 18 : (K == 7 ? 19 : -1);      // (K, 8): wave K slot 18, or wave 0 slot 19
-    constexpr int C8W = K <= 6 ? K : 0;
-    if constexpr (C8S >= 0) {
-      if (wv == C8W) {
-        const f32x4 r = pan_store(pcur + 8 * 256, lane, trsm_tile(wq, acc[C8S]));
-        GPK_EP(epoch_pan_mark(x, pcur + 8 * 256, e0 + K);)
-        if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * 8 + c, 16 * K + 4 * grp, r * inv_sigma);
-      }
-    }
-    if (wv == OWN_K) {   // z_K = R_KK^{-T} rw_K
-      f32x4 d = *(const f32x4*)&x.rw[16 * K + 4 * grp];
+  // z_K = R_KK^{-T} rw_K FIRST, by the owner of column K: every other wave's matvec of this step
+  // (phase 4c) waits for it. rw_K is read from slot K in acc layout (column 0 live): the owner
+  // completed it itself in step K-1 (row 8: wave 0's step-7 add, ordered by the kFlagBulk wait
+  // above). z_K stays unrounded fp32 and replaces rw_K in slot K (16 words, no split planes).
+  if constexpr (!kKoRhs) {
+    if (wv == OWN_K) {
+      float* zs = x.rw + 16 * K;
+      f32x4 d = *(const f32x4*)&zs[4 * grp];
       if (c != 0) d = f32x4{0.f, 0.f, 0.f, 0.f};
-      const f32x4 zk = pan_store(pcur + NB * 256, lane, trsm_tile_f32(q, d));   // (y unbounded: fp32)
-      GPK_EP(epoch_pan_mark(x, pcur + NB * 256, e0 + K);)
+      const f32x4 zk = trsm_tile_f32(q, d);   // (y unbounded: fp32)
       if (c == 0) {
+        *(f32x4*)&zs[4 * grp] = zk;
 #pragma unroll
         for (int r = 0; r < 4; ++r) x.sumz2 = __builtin_fmaf(zk[r], zk[r], x.sumz2);
         if (x.zout != nullptr) {
@@ -1118,6 +1120,79 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
             if (FULL || row + r < x.N) x.zout[(size_t)x.b * x.N + row + r] = zk[r];
         }
       }
+      GPK_EP(epoch_mark(x.vflag, kShadowZ, e0 + K, lane);)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      if (x.lane == 0) x.vflag[kFlagZ] = e0 + K;
+    }
+  }
+  // ---- 4c (defined here, run below). Right-hand side rows > K of the owned columns:
+  // rw_j += R_{K,j}^T z_K on the VALU, from the TRSM's result in acc layout (lane 16 g + c holds
+  // R_{K,j}[4 g .. 4 g + 3][c]) -- 4 FMAs per lane against one broadcast 16-byte read of
+  // z_K[4 g .. 4 g + 3], then the sum over g by two lane swaps (lanes 0-15 end up with the
+  // total). It runs behind the panel flags and the kFlagTrsm count, and on the hand-over owners
+  // behind phase 4b, so the z wait is never ahead of a tile somebody waits for; and ahead of
+  // the kFlagBulk count, which orders column 8's read-add-write in LDS (its tiles come from
+  // wave K, K <= 6, and wave 0, K = 7) from step to step (steps 0 -> 1: through z_1, which
+  // wave 0 publishes after its step-0 add).
+  const bool a_t = (K + 1 <= jA), b_t = (K + 1 <= jB);
+  constexpr int C8S = K <= 6 ? 18 : (K == 7 ? 19 : -1);      // (K, 8): wave K slot 18, or wave 0 slot 19
+  constexpr int C8W = K <= 6 ? K : 0;
+  bool c_t = false;
+  if constexpr (C8S >= 0) c_t = (wv == C8W);
+  // (ra, rb, rc: callables returning the tile -- a re-load is issued only where it is used,
+  // one tile at a time)
+  auto rhs_rows = [&](auto&& ra, auto&& rb, auto&& rc) {
+    if constexpr (!kKoRhs) {
+      if (a_t || b_t || c_t) {
+        GPK_WAITF(kFlagZ, e0 + K)
+        GPK_EP(epoch_expect(x.vflag, kShadowZ, e0 + K, 22);)
+        const f32x4 z4 = *(const f32x4*)&x.rw[16 * K + 4 * grp];
+        auto matvec = [&](const f32x4 r) {
+          float s = r[0] * z4[0];
+#pragma unroll
+          for (int m = 1; m < 4; ++m) s = __builtin_fmaf(r[m], z4[m], s);
+          s += from_upper_half_f(s);   // g: {0 + 2, 1 + 3}
+          s += from_odd_row_f(s);      // lanes 0-15: all four
+          return s;
+        };
+        const float oa = x.rw[16 * jA + c], ob = x.rw[16 * jB + c];
+        if (a_t) { const float s = oa + matvec(ra()); if (lane < 16) x.rw[16 * jA + lane] = s; }
+        if (b_t) { const float s = ob + matvec(rb()); if (lane < 16) x.rw[16 * jB + lane] = s; }
+        if constexpr (C8S >= 0) {
+          if (c_t) {
+            const float s = matvec(rc());
+            if (lane < 16) x.rw[16 * 8 + lane] += s;
+          }
+        }
+      }
+    }
+  };
+  // owners of the next step's hand-over (phase 4b)
+  constexpr int K1 = K + 1;
+  constexpr int HAW = K1 <= 6 ? K1 : (K1 == 7 ? 0 : 14 - K1);   // owner of (K1, K1+1)
+  constexpr int HBW = K1 <= 6 ? K1 : (K1 == 7 ? 1 : 14 - K1);   // owner of (K1+1, K1+1)
+  const bool ho_owner = K + 2 < NB && (wv == HAW || wv == HBW);
+  {
+    const WOp wq = w_split(q);
+    f32x4 rA = {0.f, 0.f, 0.f, 0.f}, rB = rA, rC = rA;
+    if (a_t) {
+      rA = pan_store(pcur + jA * 256, lane, trsm_tile(wq, acc[K]));
+      GPK_EP(epoch_pan_mark(x, pcur + jA * 256, e0 + K + ((kEpochSabotage && K == 3) ? 1 : 0));)
+      if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * jA + c, 16 * K + 4 * grp, rA * inv_sigma);
+    }
+    if constexpr (17 - K >= 0 && 17 - K < 18) {
+      if (b_t) {
+        rB = pan_store(pcur + jB * 256, lane, trsm_tile(wq, acc[17 - K]));
+        GPK_EP(epoch_pan_mark(x, pcur + jB * 256, e0 + K);)
+        if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * jB + c, 16 * K + 4 * grp, rB * inv_sigma);
+      }
+    }
+    if constexpr (C8S >= 0) {
+      if (wv == C8W) {
+        rC = pan_store(pcur + 8 * 256, lane, trsm_tile(wq, acc[C8S]));
+        GPK_EP(epoch_pan_mark(x, pcur + 8 * 256, e0 + K);)
+        if (x.Lb != nullptr) store4<FULL>(x.Lb, x.N, 16 * 8 + c, 16 * K + 4 * grp, rC * inv_sigma);
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     if (x.lane == 0) {
@@ -1126,9 +1201,12 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
       if constexpr (C8S >= 0) {
         if (wv == C8W) x.vflag[kFlagPan + 8] = e0 + K;
       }
-      if (wv == OWN_K) x.vflag[kFlagZ] = e0 + K;
     }
     count_in(x, kFlagTrsm);
+    // 4c straight from the registers, unless the hand-over comes first
+    if constexpr (K + 1 < NB) {
+      if (!ho_owner) rhs_rows([&] { return rA; }, [&] { return rB; }, [&] { return rC; });
+    }
   }
   // ---- 4b. hand-over HO_{K+1} = (K+1, K+2), (K+2, K+2) through panels K-1 AND K, right
   // after this step's TRSM instead of at the start of step K+1 (behind this step's bulk
@@ -1136,9 +1214,6 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
   // as its two tiles are out -- the same updates in the same order as before, so the same
   // values -- and the diagonal wave's look-ahead stops waiting for the bulk update.
   if constexpr (K + 2 < NB) {
-    constexpr int K1 = K + 1;
-    constexpr int HAW = K1 <= 6 ? K1 : (K1 == 7 ? 0 : 14 - K1);   // owner of (K1, K1+1)
-    constexpr int HBW = K1 <= 6 ? K1 : (K1 == 7 ? 1 : 14 - K1);   // owner of (K1+1, K1+1)
     constexpr int SA = K1 <= 6 ? 17 - K1 : (K1 == 7 ? 19 : K1);
     constexpr int SB = K1 <= 6 ? 16 - K1 : (K1 == 7 ? 19 : K1 + 1);
     if (wv == HAW || wv == HBW) {
@@ -1158,8 +1233,13 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
         const RbfK rk = read_rbfk(x.smem + x.rbfc);
         acc[SB] += rbf_tile<NB, FULL>(x.smem, rk, K1 + 1, K1 + 1, lane, x.N);
       }
-      // panel K (this step's TRSM)
-      GPK_WAITF(kFlagPan + K1 + 1, e0 + K)
+      // panel K (this step's TRSM). R_{K,K1+1} is this wave's own tile of a few instructions
+      // ago (column B for K1 <= 6, A for K1 >= 8): no wait on the own flag (a wave's LDS
+      // accesses are served in order); column 8's (K1 = 7) comes from wave 6, behind its flag.
+      // (Keeping the operand in registers from the TRSM to here instead of the re-load --
+      // store_split_planes and load_split_hl touch the same per-lane bytes -- spilled: 81 VGPRs
+      // in the stamps build, 1 in the product build.)
+      if constexpr (K1 == 7) { GPK_WAITF(kFlagPan + K1 + 1, e0 + K) }
       GPK_EP(pck(pcur + (K1 + 1) * 256, 17);)
       const pan_op_t p = pan_load(pcur + (K1 + 1) * 256, lane);
       const pan_op_t pl = pan_swap(p);
@@ -1174,10 +1254,15 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
         GPK_EP(epoch_mark(x.vflag, kShadowHo + 2 * (K1 & 1) + 1, e0 + K1, lane);)
         publish_tile(hN + 256, lane, acc[SB], x.vflag, kFlagHB + (K1 & 1), e0 + K1);
       }
+      // 4c of the hand-over owners: their own tiles back from panel K (hi + lo -> fp32 is exact,
+      // the registers' values; holding them across the hand-over spills)
+      rhs_rows([&] { return pan_f32(pan_load(pcur + jA * 256, lane)); },
+               [&] { return pan_f32(pan_load(pcur + jB * 256, lane)); },
+               [&] { return pan_f32(pan_load(pcur + 8 * 256, lane)); });
     }
   }
   if constexpr (GPK_EXACT_PRIO) __builtin_amdgcn_s_setprio(0);
-  GPK_WSTAMP(4, 5)  // TRSM + hand-over
+  GPK_WSTAMP(4, 5)  // TRSM + right-hand side (+ hand-over)
   if constexpr (K + 1 == NB) return 0;
   // ---- 5. the rest of the trailing update through panel K-1: rows K+1 .. of the owned columns
   if constexpr (K > 0) {
@@ -1222,25 +1307,10 @@ GPK_DEVICE int worker_step_col(f32x4 (&acc)[SLOTS], WorkerCtx& x) {
       }
     }
     GPK_WSTAMP(2, 1)  // trailing update
-    // ---- 6. right-hand side rows > K of the owned columns: rw_j += R_{K-1,j}^T z_{K-1}
-    auto rhs = [&](int j) {
-      f32x4 d = *(const f32x4*)&x.rw[16 * j + 4 * grp];
-      if (c != 0) d = f32x4{0.f, 0.f, 0.f, 0.f};
-      GPK_EP(pck(pprev + j * 256, 21);)
-      GPK_EP(pck(pprev + NB * 256, 21);)
-      d = pan_mma(pan_load(pprev + j * 256, lane), pprev + NB * 256, lane, d);
-      if (c == 0) *(f32x4*)&x.rw[16 * j + 4 * grp] = d;
-    };
-    GPK_WAITF(kFlagZ, e0 + K - 1)
-    if (K + 1 <= jA) rhs(jA);
-    if (K + 1 <= jB) rhs(jB);
-    if constexpr (K + 1 <= 8) {
-      if (wv == 1) rhs(8);
-    }
   }
-  count_in(x, kFlagBulk);   // this wave is done reading panel K-1
-  GPK_WSTAMP(5, 6)
-  // ---- 7. deferred RBF of block row K+2 and L's upper zeros
+  count_in(x, kFlagBulk);   // this wave is done reading panel K-1 (and z_K, and adding to rw_8)
+  GPK_WSTAMP(5, 6)  // bulk count
+  // ---- 6. deferred RBF of block row K+2 and L's upper zeros
   if constexpr (K + 2 < NB) {
     constexpr int R = K + 2;
     const RbfK rk = read_rbfk(x.smem + x.rbfc);
@@ -1807,15 +1877,19 @@ gpk_exact_kernel(const float* __restrict__ X, const float* __restrict__ y,
         diagval = diagval + (float)(jn - jit_prev) * sigma2;
         jit_prev = jn;
       }
-      // right-hand side: this wave's block rows of rw <- -(y - c) (fresh per attempt); in the
-      // column plan each row is initialised by the wave that owns it (columns A, B; 8: wave 1)
+      // right-hand side: this wave's block rows of rw <- -(y - c) (fresh per attempt). In the
+      // column plan each row is initialised by the wave that updates it first: columns A, B by
+      // their owner; rows 0 (no column owner) and 8 (column 8's tiles come from several waves)
+      // by wave 0, the producer of z_0 and of row 8's first update
       if constexpr (COL) {
         const int wv = launder_s(wave);
         if (lane < 16) {
           rw[16 * (15 - wv) + lane] = -rv[16 * (15 - wv) + lane];
           rw[16 * (wv + 1) + lane] = -rv[16 * (wv + 1) + lane];
-          if (wv == 1) rw[16 * 8 + lane] = -rv[16 * 8 + lane];
-          if (wv == 0) rw[lane] = -rv[lane];
+        }
+        if (wv == 0 && lane < 16) {
+          rw[lane] = -rv[lane];
+          rw[16 * 8 + lane] = -rv[16 * 8 + lane];
         }
       } else {
         for (int i = wave; i < NB; i += WK)

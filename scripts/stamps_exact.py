@@ -31,8 +31,8 @@ print(f"clock GHz (memtime/realtime): {np.mean(s[:, 8] / (s[:, 9] / 100e6)) / 1e
 for i, n in enumerate(names):
     print(f"  {n:22s} {s[:, i].mean():10.0f}  ({100 * s[:, i].mean() / tot.mean():5.1f}%)")
 for i, n in [(24, "pro: X loads+staging+max"), (25, "pro: column partials"), (26, "pro: mean"),
-             (27, "pro: centre+split"), (18, "w0: trailing upd"), (19, "w0: RHS+zeroL+RBF"), (20, "w0: TRSM"), (21, "w0: step counter"),
-             (22, "w0: hand-over"), (23, "w0: wait R_kk^-T"), (2, "diag: tile load"), (3, "diag: sweep"), (4, "diag: publish"), (13, "diag: factor"), (14, "diag: wait look-ahead tiles"), (15, "diag: look-ahead compute")]:
+             (27, "pro: centre+split"), (18, "w0: trailing upd"), (19, "w0: RBF+zeroL"), (20, "w0: z+TRSM+RHS+hand-over"), (21, "w0: bulk count"),
+             (22, "w0: row k"), (23, "w0: wait R_kk^-T"), (2, "diag: tile load"), (3, "diag: sweep"), (4, "diag: publish"), (13, "diag: factor"), (14, "diag: wait look-ahead tiles"), (15, "diag: look-ahead compute")]:
     print(f"  {n:28s} {s[:, i].mean():10.0f}  ({100 * s[:, i].mean() / tot.mean():5.1f}%)")
 
 hw = s[:, 10].astype(np.int64)
