@@ -100,6 +100,12 @@ SIGNATURES = {
     "gpk_mvn_root_max_n": (c_int, []),
     "gpk_mvn_root_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_mvn_root_grad_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gpk_mvn_root_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "gpk_mvn_root_refine_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "gpk_mvn_root_refine_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p,
+                                        c_void_p]),
     "gpk_window_gather_f32": (c_int, [c_void_p, ctypes.c_longlong, c_int, c_void_p, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }

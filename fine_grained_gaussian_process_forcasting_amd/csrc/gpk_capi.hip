@@ -6,6 +6,10 @@
 #include "gpk_kzz.h"
 #include "gpk_posterior_cov.h"
 
+size_t gpk_mvn_root_refine_ws_floats(int B, int n);
+int gpk_launch_mvn_root_refine(const float* cov, const float* R, int B, int n, float jitter, float* ws,
+                               float* Rout, hipStream_t stream);
+
 extern "C" {
 
 int gpk_version(void) { return 400; }
@@ -14,8 +18,11 @@ const char* gpk_strerror(int code) {
   if (code == 0) return "success";
   if (code < 0) {
     switch (code) {
-      case -6: return "gpk: N exceeds the supported maximum (gpk_exact_max_n)";
-      case -7: return "gpk: D too large for the LDS staging layout";
+      case -6: return "gpk: N exceeds the supported maximum (gpk_exact_max_n; gpk_mvn_root_grad_f32: n outside "
+                      "1 .. gpk_mvn_root_max_n)";
+      case -7: return "gpk: D too large for the LDS staging layout (gpk_mvn_root_grad_f32: S < 0)";
+      case -8: return "gpk: invalid argument 8 (gpk_mvn_root_grad_f32: workspace missing or not 16-byte aligned)";
+      case -9: return "gpk: invalid argument 9 (gpk_mvn_root_grad_f32: dcov is NULL)";
       default: return "gpk: invalid argument (negative code = argument index)";
     }
   }
@@ -570,6 +577,46 @@ int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int 
   if (info == nullptr) return -10;
   if (B == 0) return 0;
   return gpk_launch_mvn_root(cov, mean, eps, B, n, S, jitter, R, samples, info, (hipStream_t)stream);
+}
+
+size_t gpk_mvn_root_grad_workspace_bytes(int B, int n) {
+  if (B < 0 || n < 1 || n > kGpkMvnRootMaxN) return 0;
+  return gpk_mvn_root_grad_ws_floats(B, n) * sizeof(float);
+}
+
+int gpk_mvn_root_grad_f32(const float* R, const float* gR, const float* gsamples, const float* eps,
+                          int B, int n, int S, void* workspace, float* dcov, float* dmean, void* stream) {
+  if (R == nullptr) return -1;
+  if (S > 0 && gsamples == nullptr) return -3;
+  if (S > 0 && eps == nullptr) return -4;
+  if (B < 0) return -5;
+  if (n < 1 || n > kGpkMvnRootMaxN) return -6;
+  if (S < 0) return -7;
+  if (gpk_mvn_root_grad_workspace_bytes(B, n) > 0 && (workspace == nullptr || ((size_t)workspace & 15) != 0))
+    return -8;   // tiles are read 16 B at a time
+  if (dcov == nullptr) return -9;
+  if (B == 0) return 0;
+  return gpk_launch_mvn_root_grad(R, gR, gsamples, eps, B, n, S, (float*)workspace, dcov, dmean,
+                                  (hipStream_t)stream);
+}
+
+size_t gpk_mvn_root_refine_workspace_bytes(int B, int n) {
+  if (B < 0 || n < 1 || n > kGpkMvnRootMaxN) return 0;
+  return gpk_mvn_root_refine_ws_floats(B, n) * sizeof(float);
+}
+
+int gpk_mvn_root_refine_f32(const float* cov, const float* R, int B, int n, float jitter, void* workspace,
+                            float* Rout, void* stream) {
+  if (cov == nullptr) return -1;
+  if (R == nullptr) return -2;
+  if (B < 0) return -3;
+  if (n < 1 || n > kGpkMvnRootMaxN) return -4;
+  if (!(jitter >= 0.f)) return -5;
+  if (gpk_mvn_root_refine_workspace_bytes(B, n) > 0 && (workspace == nullptr || ((size_t)workspace & 15) != 0))
+    return -6;
+  if (Rout == nullptr || Rout == R) return -7;
+  if (B == 0) return 0;
+  return gpk_launch_mvn_root_refine(cov, R, B, n, jitter, (float*)workspace, Rout, (hipStream_t)stream);
 }
 
 int gpk_window_gather_f32(const float* table, long long n_rows, int F, const long long* rows, int B,

@@ -65,3 +65,9 @@ int gpk_launch_variational_cov_phase2(const GpkVarCovArgs& a, int O, hipStream_t
 constexpr int kGpkMvnRootMaxN = 256;
 int gpk_launch_mvn_root(const float* cov, const float* mean, const float* eps, int B, int n, int S,
                         float jitter, float* R, float* samples, int* info, hipStream_t stream);
+
+// Adjoint of the root and of the draws (gpk_mvn_root_grad.hip). Workspace: one packed 16 x 16
+// tile triangle per matrix, B * T (T + 1) / 2 * 256 floats with T = ceil(n / 16).
+size_t gpk_mvn_root_grad_ws_floats(int B, int n);
+int gpk_launch_mvn_root_grad(const float* R, const float* gR, const float* gsamples, const float* eps, int B,
+                             int n, int S, float* ws, float* dcov, float* dmean, hipStream_t stream);

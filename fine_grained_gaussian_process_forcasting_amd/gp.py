@@ -294,8 +294,9 @@ class MultivariateNormal:
         """Reparameterised sample mean + chol(Sigma) eps (upstream MultivariateNormal.rsample: the
         covariance root by psd_safe_cholesky with the jitter ladder). Off the hot path: the dense
         covariance is materialised (covariance_matrix). A CUDA fp32 distribution of n <= 256 points
-        through which no gradient can flow draws by gpk_mvn_root_f32 (factor and mean + R eps in one
-        launch, leading sample dimensions as S); every other case is torch arithmetic."""
+        draws by gpk_mvn_root_f32 (factor and mean + R eps in one launch, leading sample dimensions
+        as S), with or without gradients: its backward is gpk_mvn_root_grad_f32. Every other case
+        (CPU, fp64, n > 256, empty) is torch arithmetic."""
         cov = self.covariance_matrix
         shape = torch.Size(sample_shape) + self._mean.shape
         if base_samples is None:
@@ -303,10 +304,9 @@ class MultivariateNormal:
         elif base_samples.shape != shape:
             raise RuntimeError(f"base_samples shape {tuple(base_samples.shape)} != {tuple(shape)}")
         if (_mvn_root_eligible(cov) and self._mean.dtype == torch.float32 and base_samples.numel() > 0
-                and base_samples.is_cuda and base_samples.dtype == torch.float32
-                and _no_grad_flows(self._mean, base_samples)):
-            # eval-mode draw: the factor and mean + R eps in one launch (gpk_mvn_root_f32), the
-            # leading sample dimensions as its S; psd_safe_cholesky's ladder around it
+                and base_samples.is_cuda and base_samples.dtype == torch.float32):
+            # the factor and mean + R eps in one launch (gpk_mvn_root_f32), the leading sample
+            # dimensions as its S; psd_safe_cholesky's ladder around it
             n = self._mean.shape[-1]
             nb = self._mean.numel() // n
             _, smp = _mvn_root_ladder(cov.reshape(nb, n, n), None, self._mean.reshape(nb, n),
@@ -412,10 +412,10 @@ MVN_ROOT_MAX_N = ops.MVN_ROOT_MAX_N
 
 
 def _mvn_root_eligible(A: torch.Tensor) -> bool:
-    """A dense covariance (batch) the HIP Cholesky root takes: CUDA, fp32, 1 <= n <= 256, and no
-    gradient needed through it."""
+    """A dense covariance (batch) the HIP Cholesky root takes: CUDA, fp32, 1 <= n <= 256, with
+    or without a gradient through it (gpk::mvn_root carries its adjoint)."""
     return (torch.is_tensor(A) and A.is_cuda and A.dtype == torch.float32 and A.dim() >= 2
-            and A.shape[-1] == A.shape[-2] and 1 <= A.shape[-1] <= MVN_ROOT_MAX_N and _no_grad_flows(A))
+            and A.shape[-1] == A.shape[-2] and 1 <= A.shape[-1] <= MVN_ROOT_MAX_N)
 
 
 def _mvn_root_ladder(A: torch.Tensor, max_tries: Optional[int], mean: Optional[torch.Tensor] = None,
@@ -423,9 +423,12 @@ def _mvn_root_ladder(A: torch.Tensor, max_tries: Optional[int], mean: Optional[t
     """psd_safe_cholesky's sequence on gpk::mvn_root for A (B, n, n): jitter 0; on any failure
     the NaN check (NanError), then up to max_tries relaunches of the WHOLE batch with
     cholesky_jitter * 10^t (upstream adds the jitter to every matrix of the batch), each warning
-    NumericalWarning; NotPSDError after the last. Returns (R or None, samples or None)."""
+    NumericalWarning; NotPSDError after the last. Returns (R or None, samples or None). When a
+    gradient can flow the op also writes R, which its backward needs."""
+    keep_R = want_R or not _no_grad_flows(A, mean, eps)
+
     def launch(jit):
-        R, smp, info = torch.ops.gpk.mvn_root(A, float(jit), mean, eps, want_R)
+        R, smp, info = torch.ops.gpk.mvn_root(A, float(jit), mean, eps, keep_R)
         ok = not bool((info > 0).any())
         return ok, (R if want_R else None), (smp if eps is not None else None)
 
@@ -454,8 +457,9 @@ def psd_safe_cholesky(A: torch.Tensor, max_tries: Optional[int] = None) -> torch
     covariance roots of rsample; the hot path's factorisations run in the gfx950 kernels):
     torch.linalg.cholesky_ex, then up to max_tries retries with jitter 1e-6, 1e-5, ... (fp32;
     1e-8.. for fp64) added to the diagonal, each retry warning NumericalWarning. A CUDA fp32
-    matrix of n <= 256 that needs no gradient runs the same ladder on gpk_mvn_root_f32 (each
-    rung one launch over the whole batch); everything else takes the torch path."""
+    matrix of n <= 256 runs the same ladder on gpk_mvn_root_f32 (each rung one launch over the
+    whole batch; differentiable through gpk_mvn_root_grad_f32); everything else takes the torch
+    path."""
     if _mvn_root_eligible(A) and A.numel() > 0:
         n = A.shape[-1]
         R, _ = _mvn_root_ladder(A.reshape(-1, n, n), max_tries)

@@ -22,7 +22,9 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
                                                                                [autograd]
   gpk::variational_cov(x, Linv, Z, vstd, hyper) -> cov                        [eval only]
-  gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [eval only]
+  gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [autograd]
+  gpk::mvn_root_grad(R, gR, gsamples, eps) -> (dcov, dmean)
+  gpk::mvn_root_refine(cov, jitter, R) -> R refined (the backward's factor when jitter > 0)
 
 Reference call sites they serve: GPModel.py:10-13 + ExactMarginalLogLikelihood
 (exact_mll), ExactGPModel in eval mode (exact_posterior), DeepGP.py:33-73 VariationalStrategy (kzz_factor, variational_fwd),
@@ -499,9 +501,9 @@ def _elbo_backward(ctx, gelbo, _gflag):
 variational_elbo.register_autograd(_elbo_backward, setup_context=_elbo_setup)
 
 # ---------------------------------------------------------------------------
-# eval-mode draws: dense covariance of q(f) (gpk_variational_cov_f32) and the batched Cholesky
-# root fused with sampling (gpk_mvn_root_f32). No autograd formula: gp.py calls them only when
-# no gradient can flow and keeps the dense torch restatement for every other case.
+# draws: dense covariance of q(f) (gpk_variational_cov_f32; no autograd formula: gp.py calls it
+# only when no gradient can flow and keeps the dense torch restatement otherwise) and the batched
+# Cholesky root fused with sampling (gpk_mvn_root_f32) with its adjoint (gpk_mvn_root_grad_f32).
 # ---------------------------------------------------------------------------
 
 
@@ -537,3 +539,68 @@ def _(cov, jitter, mean=None, eps=None, want_R=True):
     return (cov.new_empty(B, n, n) if want_R else cov.new_empty(0),
             cov.new_empty(eps.shape[0], B, n) if eps is not None else cov.new_empty(0),
             cov.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("gpk::mvn_root_grad", mutates_args=(), device_types="cuda")
+def mvn_root_grad(R: Tensor, gR: Optional[Tensor] = None, gsamples: Optional[Tensor] = None,
+                  eps: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """-> (dcov (B, n, n) symmetric, dmean (B, n)): the adjoint of gpk::mvn_root."""
+    dcov, dmean = ops.mvn_root_grad(R, gR, gsamples, eps)
+    return dcov, dmean
+
+
+@mvn_root_grad.register_fake
+def _(R, gR=None, gsamples=None, eps=None):
+    B, n, _ = R.shape
+    return R.new_empty(B, n, n), R.new_empty(B, n)
+
+
+@torch.library.custom_op("gpk::mvn_root_refine", mutates_args=(), device_types="cuda")
+def mvn_root_refine(cov: Tensor, jitter: float, R: Tensor) -> Tensor:
+    """One refinement step of the fp32 root with an fp64 residual (gpk_mvn_root_refine_f32)."""
+    return ops.mvn_root_refine(cov, jitter, R)
+
+
+@mvn_root_refine.register_fake
+def _(cov, jitter, R):
+    return torch.empty_like(R)
+
+
+def _mvn_root_setup(ctx, inputs, output):
+    cov, jitter, mean, eps, want_R = inputs
+    R, samples, info = output
+    ctx.has_eps = eps is not None
+    ctx.want_R = want_R
+    ctx.mean_shape = mean.shape if mean is not None else None
+    ctx.jitter = jitter
+    # a rung with jitter: the matrix is near-singular, the backward refines the fp32 factor
+    ctx.save_for_backward(R, eps, cov if jitter > 0.0 and want_R else None)
+    ctx.mark_non_differentiable(info)
+    ctx.set_materialize_grads(False)
+
+
+@torch.autograd.function.once_differentiable
+def _mvn_root_backward(ctx, gR, gsamples, _ginfo):
+    R, eps, cov = ctx.saved_tensors
+    if not ctx.want_R:
+        raise RuntimeError("gpk::mvn_root was called with want_R=False; its backward needs the factor: "
+                           "call it with want_R=True when a gradient can flow")
+    if not ctx.has_eps or gsamples is None:
+        gsamples = eps_k = None
+    else:
+        gsamples, eps_k = gsamples.contiguous(), eps
+    if gR is not None:
+        gR = gR.contiguous()
+    if cov is not None:
+        # the ladder engaged: the fp32 factor is cond * 2^-24 off, which the adjoint amplifies
+        R = torch.ops.gpk.mvn_root_refine(cov, ctx.jitter, R)
+    dcov, dmean = torch.ops.gpk.mvn_root_grad(R, gR, gsamples, eps_k)
+    deps = None
+    if ctx.has_eps and ctx.needs_input_grad[3] and gsamples is not None:
+        deps = torch.einsum("bji,sbj->sbi", R, gsamples)   # R^T g per draw
+    if ctx.mean_shape is None or not ctx.needs_input_grad[2]:
+        dmean = None
+    return dcov, None, dmean, deps, None
+
+
+mvn_root.register_autograd(_mvn_root_backward, setup_context=_mvn_root_setup)

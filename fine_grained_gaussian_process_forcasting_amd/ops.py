@@ -861,6 +861,76 @@ def mvn_root(cov: torch.Tensor, jitter: float = 0.0, mean: Optional[torch.Tensor
     return R, samples, info
 
 
+def mvn_root_refine(cov: torch.Tensor, jitter: float, R: torch.Tensor) -> torch.Tensor:
+    """One refinement step of the fp32 root R of cov + jitter I with an fp64 residual
+    (include/gpk.h::gpk_mvn_root_refine_f32): (B, n, n) -> (B, n, n), for the adjoint of a
+    near-singular covariance. Memory per call: the workspace (B * T (T + 1) KiB) + the output."""
+    if cov.dim() != 3 or cov.shape[-1] != cov.shape[-2] or cov.shape != R.shape:
+        raise ValueError(f"cov and R must be (B, n, n), got {tuple(cov.shape)}, {tuple(R.shape)}")
+    B, n, _ = cov.shape
+    if not 1 <= n <= MVN_ROOT_MAX_N:
+        raise ValueError(f"gpk_mvn_root_refine_f32 takes 1 <= n <= {MVN_ROOT_MAX_N}, got n = {n}")
+    _require_device(cov, R)
+    dev = cov.device
+    cov = cov.detach().contiguous().float()
+    R = R.detach().contiguous().float()
+    out = torch.empty_like(R)
+    if B == 0:
+        return out
+    lib = _native.lib()
+    ws = torch.empty(max(1, lib.gpk_mvn_root_refine_workspace_bytes(B, n) // 4), device=dev, dtype=torch.float32)
+    rc = lib.gpk_mvn_root_refine_f32(cov.data_ptr(), R.data_ptr(), B, n, float(jitter), ws.data_ptr(),
+                                     out.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_mvn_root_refine_f32")
+    return out
+
+
+def mvn_root_grad(R: torch.Tensor, gR: Optional[torch.Tensor] = None, gsamples: Optional[torch.Tensor] = None,
+                  eps: Optional[torch.Tensor] = None, want_dmean: bool = True):
+    """Adjoint of ``mvn_root`` in ONE gfx950 launch (include/gpk.h::gpk_mvn_root_grad_f32): from
+    the forward's factor R (B, n, n), the gradient gR (B, n, n; lower triangle read) of R and / or
+    the gradient gsamples (S, B, n) of the draws made with eps (S, B, n), returns (dcov (B, n, n)
+    symmetric, dmean (B, n) or None). gR None and no gsamples gives zeros. Memory per call: the
+    workspace (B * T (T + 1) / 2 KiB, T = ceil(n / 16)) + the outputs."""
+    if R.dim() != 3 or R.shape[-1] != R.shape[-2]:
+        raise ValueError(f"R must be (B, n, n), got {tuple(R.shape)}")
+    B, n, _ = R.shape
+    if not 1 <= n <= MVN_ROOT_MAX_N:
+        raise ValueError(f"gpk_mvn_root_grad_f32 takes 1 <= n <= {MVN_ROOT_MAX_N}, got n = {n}")
+    if (gsamples is None) != (eps is None):
+        raise ValueError("gsamples and eps are given together")
+    _require_device(R)
+    dev = R.device
+    R = R.detach().contiguous().float()
+    if gR is not None:
+        _require_device(gR)
+        if tuple(gR.shape) != (B, n, n):
+            raise ValueError(f"gR must be (B, n, n) = {(B, n, n)}, got {tuple(gR.shape)}")
+        gR = gR.detach().contiguous().float()
+    S = 0
+    if gsamples is not None:
+        _require_device(gsamples, eps)
+        if gsamples.dim() != 3 or tuple(gsamples.shape[1:]) != (B, n) or gsamples.shape != eps.shape:
+            raise ValueError(f"gsamples and eps must be (S, B, n) with (B, n) = {(B, n)}; got "
+                             f"{tuple(gsamples.shape)}, {tuple(eps.shape)}")
+        S = gsamples.shape[0]
+        gsamples = gsamples.detach().contiguous().float()
+        eps = eps.detach().contiguous().float()
+    dcov = torch.empty(B, n, n, device=dev, dtype=torch.float32)
+    dmean = torch.empty(B, n, device=dev, dtype=torch.float32) if want_dmean else None
+    if B == 0:
+        return dcov, dmean
+    lib = _native.lib()
+    nbytes = lib.gpk_mvn_root_grad_workspace_bytes(B, n)
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    rc = lib.gpk_mvn_root_grad_f32(
+        R.data_ptr(), gR.data_ptr() if gR is not None else None, gsamples.data_ptr() if S > 0 else None,
+        eps.data_ptr() if S > 0 else None, B, n, S, ws.data_ptr(), dcov.data_ptr(),
+        dmean.data_ptr() if dmean is not None else None, _stream_ptr(dev))
+    _native.check(rc, "gpk_mvn_root_grad_f32")
+    return dcov, dmean
+
+
 @dataclass
 class VariationalAdjointBatched:
     dX: torch.Tensor      # (O, B, N, D) per output (shared inputs: the caller sums over O)

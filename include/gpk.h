@@ -470,6 +470,67 @@ int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int 
                      float jitter, float* R, float* samples, int* info, void* stream);
 
 /*
+ * Adjoint of gpk_mvn_root_f32: per matrix b, from the forward's factor R (R R^T = cov + jitter I)
+ * and the upstream gradients of R and of the draws,
+ *   Rbar  = tril(gR) + tril(sum_s gsamples[s, b, :] (x) eps[s, b, :])      (n x n, lower)
+ *   P     = Phi(R^T Rbar)        Phi: lower triangle, diagonal halved
+ *   Sbar  = R^{-T} P R^{-1}
+ *   dcov  = (Sbar + Sbar^T) / 2                                            (dense)
+ *   dmean = sum_s gsamples[s, b, :]                                        (ascending s)
+ * The forward reads cov as a symmetric matrix through its lower triangle; dcov is the symmetric
+ * gradient torch.linalg.cholesky's backward returns, symmetric bit for bit. The jitter has no
+ * gradient. One workgroup per matrix: R, then R^{-1} (inverted in place, block row by block
+ * row), as packed 16 x 16 tiles in LDS; P and P R^{-1} stream through the workspace; every
+ * product on the fp32 MFMA in a fixed order, no atomics: run-to-run deterministic. Allocates
+ * nothing and keeps no pointers.
+ *
+ * Replaces (reference): the autograd backward of upstream linear_operator utils/cholesky.py
+ * psd_safe_cholesky (torch.linalg.cholesky's backward) and of distributions/
+ * multivariate_normal.py rsample's root matmul, which train.py:166 ``loss.backward()`` runs
+ * through the skip-input draw of denoising_model/DeepGP.py:62-64 ``x.rsample()``.
+ *
+ * Memory per call: the workspace, gpk_mvn_root_grad_workspace_bytes(B, n) bytes
+ * (B * T (T + 1) / 2 KiB with T = ceil(n / 16): 136 KiB per matrix at n = 256), plus the
+ * B * n^2 floats of dcov. The query returns 0 for a shape the call does not accept.
+ *
+ * R : (B, n, n) float, the forward's output; the upper triangle is ignored
+ * gR : (B, n, n) float or NULL; only the lower triangle is read
+ * gsamples, eps : (S, B, n) float; both required when S > 0, ignored when S = 0
+ * workspace : device memory of the size above, 16-byte aligned
+ * dcov : (B, n, n) float out   dmean : (B, n) float out or NULL
+ * gR NULL with S = 0 zero-fills dcov. 1 <= n <= gpk_mvn_root_max_n() = 256, B >= 0 (B = 0
+ * launches nothing).
+ */
+size_t gpk_mvn_root_grad_workspace_bytes(int B, int n);
+int gpk_mvn_root_grad_f32(const float* R, const float* gR, const float* gsamples, const float* eps,
+                          int B, int n, int S, void* workspace, float* dcov, float* dmean, void* stream);
+
+/*
+ * One refinement step of the fp32 root of gpk_mvn_root_f32, per matrix b:
+ *   E = cov + jitter I - R R^T   (accumulated in fp64)      Y = R^{-1} E R^{-T}
+ *   Rout = R + R Phi(Y)          Phi: lower triangle, diagonal halved
+ * For a near-singular cov (one that needed the jitter ladder) the fp32 factor is
+ * cond * 2^-24 from the true one and its gradient amplifies that once more; Rout is as close
+ * to the factor of cov + jitter I as fp32 storage allows. The autograd formula of gpk::mvn_root
+ * feeds it to gpk_mvn_root_grad_f32 when the rung that succeeded had jitter > 0. One workgroup
+ * per matrix, tiles, inversion and MFMA as gpk_mvn_root_grad_f32; fixed order, no atomics.
+ *
+ * Replaces (reference): nothing upstream computes this; it stands in for the accuracy the
+ * backward of psd_safe_cholesky would have on an fp64 factor (train.py:166 through
+ * denoising_model/DeepGP.py:62-64 when the ladder engages).
+ *
+ * Memory per call: the workspace, gpk_mvn_root_refine_workspace_bytes(B, n) bytes
+ * (B * T (T + 1) KiB, T = ceil(n / 16)); 0 for a shape the call does not accept.
+ *
+ * cov : (B, n, n) float, lower triangle read   R : (B, n, n) float, lower triangle read
+ * workspace : 16-byte aligned   Rout : (B, n, n) float out, upper triangle zero; not R itself
+ * 1 <= n <= gpk_mvn_root_max_n(), B >= 0, jitter >= 0.
+ */
+size_t gpk_mvn_root_refine_workspace_bytes(int B, int n);
+int gpk_mvn_root_refine_f32(const float* cov, const float* R, int B, int n, float jitter, void* workspace,
+                            float* Rout, void* stream);
+
+/*
  * GPU-resident training-window gather:
  *   for window b with first row r = rows[b] of the (id, time)-sorted table:
  *     enc[b] = table[r      : r + n_enc]                  (n_enc, F)
