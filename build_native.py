@@ -1,6 +1,10 @@
 """Build libgpk.so (HIP kernels + C ABI) for gfx950 in-tree.
 
-Usage: python build_native.py [--force]
+Usage: python build_native.py [--force] [-DNAME=VALUE ... --out-dir DIR]
+Every csrc/*.hip is one unit (the variational path: gpk_variational.hip and one gpk_var_*.hip per
+kernel path); a unit is recompiled when it, a local header it includes or the flags change.
+-D switches that several units read (GPK_VAR_LREG, GPK_VAR_REG, GPK_KGRAM_SPL, ...) belong here,
+with an --out-dir of their own, so that every unit sees them.
 The .so lands in fine_grained_gaussian_process_forcasting_amd/_lib/ (git-ignored, but it
 travels to the GPU box with the gpurun snapshot).
 """

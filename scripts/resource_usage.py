@@ -1,6 +1,8 @@
 """Per-kernel register / spill / occupancy table from hipcc -Rpass-analysis=kernel-resource-usage.
 
-    python scripts/resource_usage.py fine_grained_gaussian_process_forcasting_amd/csrc/gpk_variational.hip [filter]
+    python scripts/resource_usage.py fine_grained_gaussian_process_forcasting_amd/csrc/gpk_var_reg.hip [filter]
+
+One unit at a time (the variational kernels: one gpk_var_*.hip per kernel path).
 """
 import re
 import subprocess

@@ -52,14 +52,13 @@ def test_argument_validation_without_device():
 def test_variational_adjoint_entry_validation_without_device():
     from fine_grained_gaussian_process_forcasting_amd import _native
     lib = _native.lib()
-    one = ctypes.c_void_p(16)
+    one = ctypes.c_void_p(16)  # never dereferenced: validation returns first
     ws = lib.gpk_variational_adjoint_workspace_bytes(4, 192, 256, 32)
     # dA and K_ZX (M x B*N fp32 each) dominate the workspace
     assert ws >= 2 * 256 * 4 * 192 * 4
     assert lib.gpk_variational_adjoint_workspace_bytes(4, 192, 257, 32) == 0
     assert lib.gpk_variational_adjoint_workspace_bytes(4, 192, 64, 65) == 0
     args = [one] * 8 + [2, 16, 8, 4] + [one] * 5 + [None]
-    assert lib.gpk_variational_adjoint_f32(*args) != 0 or True  # (pointer validity not checkable)
     for idx, code in [(0, -1), (6, -7), (12, -13), (13, -14), (14, -15), (15, -16), (16, -17)]:
         bad = list(args); bad[idx] = None
         assert lib.gpk_variational_adjoint_f32(*bad) == code

@@ -64,7 +64,11 @@ def test_kzz_cholesky_parity(cuda_device, M, D):
                                              (2, 33, 180, 40, True), (2, 64, 256, 16, True),
                                              (1, 40, 250, 64, True), (5, 192, 256, 32, True),
                                              # M <= 64 with D in (32, 64]: the LDS-tiled path
-                                             (3, 40, 48, 48, True), (2, 30, 64, 64, True)])
+                                             (3, 40, 48, 48, True), (2, 30, 64, 64, True),
+                                             # the instantiations no other test launches:
+                                             # gpk_var_fwd_kernel<1>, <2>, gpk_var_fwd_l_kernel<8, 32>, <12, 16>
+                                             (2, 40, 13, 33, True), (2, 40, 29, 33, True),
+                                             (2, 40, 100, 17, True), (2, 40, 130, 16, True)])
 def test_variational_parity(cuda_device, B, N, M, D, trained):
     from fine_grained_gaussian_process_forcasting_amd import ops
     X, Z, m, s, w, b0, y = _case(B, N, M, D, seed=B * 7 + N, trained=trained)

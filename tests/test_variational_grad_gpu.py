@@ -114,7 +114,11 @@ def test_variance_clamp_gradient_mask(cuda_device, M, saved):
                                      # M > 64 register-resident adjoint: every row-block
                                      # count, ragged M / N, D up to the DQ = 64 variant
                                      (3, 70, 100, 7), (2, 50, 96, 20), (2, 33, 180, 30),
-                                     (2, 41, 250, 32), (2, 45, 90, 40), (2, 30, 120, 64)])
+                                     (2, 41, 250, 32), (2, 45, 90, 40), (2, 30, 120, 64),
+                                     # the LDS-tiled adjoint's instantiations no other test launches:
+                                     # gpk_var_adj_kernel<1, 64>, <2, 64>, and <12, 64>, <16, 64> (M > 64
+                                     # where the L^{-1} plan does not fit; no saved state either)
+                                     (2, 40, 13, 33), (2, 40, 29, 33), (2, 40, 130, 33), (2, 40, 250, 33)])
 @pytest.mark.parametrize("saved", [False, True])
 def test_variational_grads_reference_shapes(cuda_device, B, N, M, D, saved):
     """The backward at the reference's GP shapes (M=256 default, DeepGP.py:15; cfg 5's
