@@ -2,9 +2,11 @@
 
 Usage: python build_native.py [--force] [-DNAME=VALUE ... --out-dir DIR]
 Every csrc/*.hip is one unit (the variational path: gpk_variational.hip and one gpk_var_*.hip per
-kernel path); a unit is recompiled when it, a local header it includes or the flags change.
--D switches that several units read (GPK_VAR_LREG, GPK_VAR_REG, GPK_KGRAM_SPL, ...) belong here,
-with an --out-dir of their own, so that every unit sees them.
+kernel path; the exact forward: gpk_exact.hip and one gpk_exact_nb*.hip per size group); a unit is
+recompiled when it, a local header it includes or the flags change.
+-D switches that several units read (GPK_VAR_LREG, GPK_VAR_REG, GPK_KGRAM_SPL, ..., and the
+gpk_exact_dev.h switches of the exact units) belong here, with an --out-dir of their own, so that
+every unit sees them.
 The .so lands in fine_grained_gaussian_process_forcasting_amd/_lib/ (git-ignored, but it
 travels to the GPU box with the gpurun snapshot).
 """
@@ -61,6 +63,14 @@ def _digest(paths, extra=""):
     return h.hexdigest()
 
 
+def _compile(src, obj, flags):
+    cmd = [HIPCC, *flags, "-I", os.path.join(ROOT, "include"), "-c", src, "-o", obj]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
+    return cmd, r.stderr
+
+
 def build(force: bool = False, verbose: bool = True, defines=(), out_dir: str = OUT_DIR) -> str:
     """Compile every csrc/*.hip for gfx950 and link libgpk.so into out_dir.
     `defines` (e.g. ["GPK_SPLIT_UPDATE=0"]) and a non-default out_dir are for
@@ -82,14 +92,11 @@ def build(force: bool = False, verbose: bool = True, defines=(), out_dir: str = 
 
     def compile_one(job):
         src, obj, stamp, dig = job
-        cmd = [HIPCC, *flags, "-I", os.path.join(ROOT, "include"), "-c", src, "-o", obj]
         if verbose:
-            print("[build]", " ".join(os.path.basename(c) if c.startswith(ROOT) else c for c in cmd), flush=True)
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
-        if r.stderr.strip() and verbose:
-            print(r.stderr, file=sys.stderr)
+            print("[build]", " ".join(flags), os.path.basename(src), flush=True)
+        _, err = _compile(src, obj, flags)
+        if err.strip() and verbose:
+            print(err, file=sys.stderr)
         with open(stamp, "w") as f:
             f.write(dig)
 
@@ -107,8 +114,9 @@ def build(force: bool = False, verbose: bool = True, defines=(), out_dir: str = 
 
 
 # Measurement-only variant builds of the exact kernel (bench.py's "fp32_update" note: the
-# pure-fp32 MFMA trailing update beside the split-f16 product path). Only gpk_exact.hip is
-# recompiled (N = 128 / 256 instantiations); the other objects of the main build are linked in.
+# pure-fp32 MFMA trailing update beside the split-f16 product path). Only the units that read
+# gpk_exact_dev.h are recompiled (N = 128 / 256 instantiations); the other objects of the main
+# build are linked in.
 VARIANTS = {"f32update": ["GPK_SPLIT_UPDATE=0", "GPK_EXACT_DEV=1"]}
 
 
@@ -117,24 +125,24 @@ def build_variant(name: str, verbose: bool = True) -> str:
     out_dir = os.path.join(PKG, "_lib_variants", name)
     os.makedirs(out_dir, exist_ok=True)
     lib_path = os.path.join(out_dir, "libgpk.so")
-    src = os.path.join(CSRC, "gpk_exact.hip")
-    obj = os.path.join(out_dir, "gpk_exact.hip.o")
+    dev_h = os.path.join(CSRC, "gpk_exact_dev.h")
+    own = [x for x in sources() if dev_h in included(x)]
+    own_objs = [os.path.join(out_dir, os.path.basename(x) + ".o") for x in own]
     flags = FLAGS + [f"-D{d}" for d in VARIANTS[name]]
-    objs = [os.path.join(OUT_DIR, os.path.basename(x) + ".o") for x in sources() if not x.endswith("gpk_exact.hip")]
-    # the digest covers the variant's own source + flags AND the main-build objects it links
+    objs = [os.path.join(OUT_DIR, os.path.basename(x) + ".o") for x in sources() if x not in own]
+    # the digest covers the variant's own sources + flags AND the main-build objects it links
     # in (their .sha stamps), so a change to any other kernel relinks the variant too
     linked = "".join(open(o + ".sha").read() if os.path.exists(o + ".sha") else o for o in objs)
-    dig = _digest([src] + sorted(included(src)), " ".join(flags) + main_lib + linked)
-    stamp = obj + ".sha"
+    closure = sorted(set(own).union(*(included(x) for x in own)))
+    dig = _digest(closure, " ".join(flags) + main_lib + linked)
+    stamp = os.path.join(out_dir, "variant.sha")
     if os.path.exists(lib_path) and os.path.exists(stamp) and open(stamp).read() == dig:
         return lib_path
-    cmd = [HIPCC, *flags, "-I", os.path.join(ROOT, "include"), "-c", src, "-o", obj]
     if verbose:
         print("[build variant]", name, " ".join(VARIANTS[name]), flush=True)
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed for the {name} variant:\n{r.stderr}")
-    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, obj, "-o", lib_path],
+    with ThreadPoolExecutor(max_workers=min(8, len(own))) as ex:
+        list(ex.map(lambda so: _compile(so[0], so[1], flags), zip(own, own_objs)))
+    r = subprocess.run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, *own_objs, "-o", lib_path],
                        capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed for the {name} variant:\n{r.stderr}")

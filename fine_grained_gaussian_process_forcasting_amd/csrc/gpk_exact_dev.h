@@ -1,55 +1,40 @@
-// Build switches and development-only instrumentation of the exact kernel (gpk_exact.hip).
+// Build switches and development-only instrumentation of the exact kernel (gpk_exact_kernel.h,
+// compiled by the gpk_exact_nb*.hip units).
 //
-// Product builds (build_native.py) define none of these macros: every switch below defaults
+// Product builds (build_native.py) define none of these macros: the switch below defaults
 // to the shipped, measured setting; the knockouts compile to `false`; the stamp macros only
 // expand inside kernels instantiated with STAMPS = true (the gpk_debug_exact_stamps entry,
-// scripts/r05/stamps_col.py). A/B builds: scripts/ab_build_one.sh <name> gpk_exact.hip -DNAME=v.
+// scripts/stamps_exact.py). A/B builds: scripts/ab_build_one.sh <name> 'gpk_exact_nb*.hip' -DNAME=v
+// (every unit that includes this header; build_native.build_variant does the same).
 #pragma once
 
-// ---- design switches: the defaults are the measured winners ----
-#ifndef GPK_EXACT_WBIG
-#define GPK_EXACT_WBIG 8
-#endif
+// ---- the one design switch left: both sides ship (build_native.VARIANTS["f32update"]) ----
 #ifndef GPK_SPLIT_UPDATE
-#define GPK_SPLIT_UPDATE 1
+#define GPK_SPLIT_UPDATE 1   // 1: split-f16 trailing update; 0: pure fp32 MFMA (bench.py's fp32_update note)
 #endif
-#ifndef GPK_EXACT_SMALLB
-#define GPK_EXACT_SMALLB 1   // B <= CUs: one window per CU with 16 waves (launch_exact_nb)
-#endif
-#ifndef GPK_EXACT_DIAG_ALONE
-#define GPK_EXACT_DIAG_ALONE 1   // 1: small-batch layout (NB <= 8) with the diagonal wave alone on its SIMD
-                                 // (12 workers; 0: 15 workers, the round-5 layout)
-#endif
-#ifndef GPK_EXACT_PRIO_RHS
-#define GPK_EXACT_PRIO_RHS 1   // raise the worker priority already at the right-hand side (0: at the TRSM)
-#endif
-#ifndef GPK_EXACT_PRIO
-#define GPK_EXACT_PRIO 1   // workers raise their issue priority to this for the hand-over and the TRSM
-                           // (0: off; 1 measured 2.5 % faster per launch, scripts/gpu_ab_prio.sh)
-#endif
-#ifndef GPK_DIAG_DPP
-#define GPK_DIAG_DPP 1   // diagonal sweep as DPP-broadcast FMAs (gpk_diag_dpp.inc); 0 = readlane form
-#endif
-#ifndef GPK_DIAG_PERMLANE
-#define GPK_DIAG_PERMLANE 0   // 1: the diagonal wave gathers its sweep operand by permlane swaps from the
-                              // look-ahead's registers (measured 0.6-0.8 us SLOWER per launch at B = 64 / 128);
-                              // 0: through its LDS tile
-#endif
-#ifndef GPK_DIAG_FINISH_LATE
-#define GPK_DIAG_FINISH_LATE 0   // 1: step k's L block + log|T| after the look-ahead MFMAs (measured
-                                 // slower: the in-order wave puts them on the chain); 0: before the wait
-#endif
-#ifndef GPK_EXACT_COL
-#define GPK_EXACT_COL 1   // 1: column-ownership worker plan for N = 256 at 8 waves (worker_step_col)
-#endif
-#ifndef GPK_LST_AUX
-#define GPK_LST_AUX 17   // L stores: -1 plain global stores; >= 0 buffer stores with this cache-policy aux
-                         // (17 = sc0 sc1: write-through, the lines leave L2 -- 64.5 -> 59.2 us per B=512 launch)
-#endif
+constexpr int kWorkerPrio = 1;   // workers raise their issue priority to this from the right-hand side through
+                                 // the TRSM and for the hand-over (2.5 % + ~2 % per launch, profiles/r03_exact_prio_ab.txt)
+constexpr int kLStoreAux = 17;   // cache policy of the L buffer stores (sc0 sc1: write-through, the lines leave L2)
+
+// Retired switches: one line each, what was tried; the losing sides are gone from the source and
+// the measured verdicts stay in DESIGN.md §4.1 and the named record under profiles/.
+//   GPK_EXACT_WBIG=16        16 waves at two windows per CU for NB >= 12 (8 kept)
+//   GPK_EXACT_SMALLB=0       no one-window-per-CU, 16-wave layout for B <= CUs (r04_exact_ab.jsonl)
+//   GPK_EXACT_DIAG_ALONE=0   15 workers at NB <= 8 instead of the diagonal wave alone on its SIMD
+//                            (r06_exact_alone_ab.txt, r06_exact_alone13_ab.txt)
+//   GPK_EXACT_PRIO=0         no raised worker priority; GPK_EXACT_PRIO_RHS=0: raised only at the TRSM
+//                            (r03_exact_prio_ab.txt)
+//   GPK_DIAG_DPP=0           diagonal sweep as readlane broadcasts into pinned SGPRs (r03_mb_diag.txt)
+//   GPK_DIAG_PERMLANE=1      sweep operand by permlane swaps from the look-ahead's registers: slower
+//                            than through the LDS tile; GPK_DIAG_FINISH_LATE=1: step k's L block and
+//                            log|T| behind the look-ahead MFMAs: slower (r06_exact_ab.txt)
+//   GPK_EXACT_COL=0          split-barrier plan at N = 256 with 8 waves
+//   GPK_LST_AUX=-1           plain global L stores, 64.5 vs 59.2 us per B = 512 launch
 
 // ---- development only ----
 #ifndef GPK_EXACT_DEV
-#define GPK_EXACT_DEV 0   // 1: only the N = 128 / 256 instantiations (fast A/B compiles)
+#define GPK_EXACT_DEV 0   // 1: only the N = 128 / 256 instantiations (fast A/B compiles): units without
+                          // NB = 8 or 16 compile to a launcher that returns -6 (launch_exact_case)
 #endif
 #ifndef GPK_TMO_DEBUG
 #define GPK_TMO_DEBUG 0   // 1 (debug builds): a timed-out window's info = flag index | target << 8

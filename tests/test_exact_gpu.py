@@ -265,3 +265,40 @@ def test_exact_layout_ladder_and_failures(cuda_device, B, N, D, dup, nanw):
         assert np.all(np.triu(L[b], 1) == 0.0)
         err = np.linalg.norm(L[b] @ L[b].T - K) / np.linalg.norm(K)
         assert err <= 1e-5, (b, t, err)
+
+
+def _every_instantiation():
+    """(NB, N, D, two windows per CU): NB = 1..16, full and padded tiles, both prologues, and
+    from NB = 6 (where the launcher has two layouts) both layouts."""
+    return [(nb, n, d, two) for nb in range(1, 17) for n in (16 * nb, 16 * nb - 3) for d in (5, 40)
+            for two in ((False, True) if nb >= 6 else (False,))]
+
+
+@pytest.mark.parametrize("NB,N,D,two_per_cu", _every_instantiation())
+def test_exact_every_instantiation(cuda_device, NB, N, D, two_per_cu):
+    """Every product instantiation of the exact kernel is launched: NB = 1..16, FULL (N = 16 NB) and
+    padded (N = 16 NB - 3), D = 5 (fast prologue, one ragged 16-column chunk) and D = 40 (three
+    chunks, staged prologue), at B = 3 (one window per CU: 16 waves from NB = 6) and, from NB = 6,
+    at B = compute units + 1 (two windows per CU). Window 1 is N copies of one point at zero noise
+    (the in-kernel jitter ladder restarts it); the others are regular."""
+    B = torch.cuda.get_device_properties(cuda_device).multi_processor_count + 1 if two_per_cu else 3
+    X, y = _inputs(B, N, D, seed=NB * 100 + D)
+    X[1] = X[1, :1].expand(N, D)
+    ls, noise = 0.3, 0.0
+    out = _run(cuda_device, X, y, ls, 1.0, 0.0, noise)
+    info = out.info.cpu().numpy()
+    assert info[1] < 0, info[1]
+    L1 = out.L[1].cpu().double().numpy()
+    K = np.ones((N, N)) + _ladder_jitter(-int(info[1])) * np.eye(N)
+    err = np.linalg.norm(L1 @ L1.T - K) / np.linalg.norm(np.ones((N, N)))
+    assert err <= 1e-5, (int(info[1]), err)
+    assert (np.delete(info, 1) == 0).all(), info
+    sel = [0, 2, B - 1]
+    ref = O.exact_mll(X[sel].double().numpy(), y[sel].double().numpy(), ls, 1.0, 0.0, noise)
+    assert (ref.info == 0).all()
+    L = out.L[sel].cpu().double().numpy()
+    assert np.all(np.triu(L, 1) == 0.0), "upper triangle must be exactly zero"
+    assert _rel_fro(L, ref.L).max() <= 1e-4
+    assert _rel_fro(out.z[sel].cpu().double().numpy(), ref.z).max() <= 1e-4
+    mll = out.mll[sel].cpu().double().numpy()
+    assert np.max(np.abs(mll - ref.mll) / np.abs(ref.mll)) <= 1e-4
