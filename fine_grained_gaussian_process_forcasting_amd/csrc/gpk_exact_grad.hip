@@ -766,7 +766,15 @@ GPK_DEVICE void grad_gram_split_body(const GpkExactGradArgs& a, float* smem) {
   lds_barrier();
   const float s2 = hyp[0];
   const float gw = a.gout[b];
-  const float gs = gw / (2.f * (float)N);
+  // The contractions run with |gout| and the sign goes (exactly) onto the outputs: the f16
+  // MFMA's accumulation does not round symmetrically in sign, so Wx of -W is not -(Wx of W),
+  // and after the cancellation in xs w1 - Wx the two differed by thousands of ulps.
+  // (The sign is taken where it is applied, behind opaque_v: computed here it moves the wait for
+  // gout's load, and for everything in flight with it, to the top of the gram: 0.3 us.)
+  const float gs = __builtin_fabsf(gw / (2.f * (float)N));
+  auto gout_sign = [&]() -> float {
+    return __builtin_copysignf(1.f, __builtin_bit_cast(float, opaque_v(__builtin_bit_cast(int, gw))));
+  };
   float wscale = 1.f;
   {
     float amax = 0.f, tmax = 0.f;
@@ -854,6 +862,7 @@ GPK_DEVICE void grad_gram_split_body(const GpkExactGradArgs& a, float* smem) {
 #pragma unroll
   for (int r = 0; r < 4; ++r) w1r[r] = __shfl(w1p, 4 * g + r, 64);
   float* part = pl + I * (2 + DP);
+  const float gm2 = -2.f * gout_sign();   // dxs = -2 sign(gout) (xs w1 - Wx)
 #pragma unroll
   for (int q = 0; q < DQ; ++q) {
     const int d = 16 * q + c;
@@ -865,7 +874,7 @@ GPK_DEVICE void grad_gram_split_body(const GpkExactGradArgs& a, float* smem) {
       const float x = (float)xh[row * RS + d] + (float)xl[row * RS + d];
       const float e = x * w1r[r] - wx[q][r];   // = -dxs / 2
       if ((FULL || row < N) && d < D) {
-        if (a.dX != nullptr && !GPK_GRAD_STAMPS) a.dX[((size_t)b * N + row) * D + d] = -2.f * e * ilq;
+        if (a.dX != nullptr && !GPK_GRAD_STAMPS) a.dX[((size_t)b * N + row) * D + d] = gm2 * e * ilq;
         lp = __builtin_fmaf(x, e, lp);
       }
     }
@@ -889,6 +898,7 @@ GPK_DEVICE void grad_gram_split_body(const GpkExactGradArgs& a, float* smem) {
     float sacc = 0.f;
     if (f >= 0)
       for (int I2 = 0; I2 < NB; ++I2) sacc += pl[I2 * (2 + DP) + f];
+    sacc *= gout_sign();   // the partials were summed for |gout|
     if (t == 64) o[0] = sacc;
     if (t == 65) o[1] = sacc;
     if (t == 66) o[2] = gw * wsb[ws.asum] / (float)N;

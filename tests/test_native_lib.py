@@ -119,6 +119,34 @@ def test_grad_entry_validation_without_device():
     assert lib.gpk_exact_mll_grad_f32(*bad) == 0   # B = 0: nothing to do
 
 
+def test_grad_workspace_bytes_every_n():
+    """gpk_exact_grad_workspace_bytes against a restatement of the kernels' layout (grad_ws in
+    csrc/gpk_exact_grad.hip) for every N of the register path: NT = NB (NB + 1) / 2 lower K^-1
+    tiles of 256 floats, alpha (16 NB), the column means (64), sum(alpha) (4) and NB block-row
+    partials of 2 + 64, rounded up to 64 floats per window; linear in B; the blocked path's
+    size is positive up to N = 800, and 0 beyond."""
+    from fine_grained_gaussian_process_forcasting_amd import _native
+    lib = _native.lib()
+
+    def per_window(N):
+        NB = (N + 15) // 16
+        NT = NB * (NB + 1) // 2
+        per = NT * 256 + 16 * NB + 64 + 4 + NB * 66
+        return (per + 63) // 64 * 64
+
+    for N in range(1, 257):
+        one = lib.gpk_exact_grad_workspace_bytes(1, N)
+        assert one == 4 * per_window(N), N
+        for B in (2, 3, 7, 512):
+            assert lib.gpk_exact_grad_workspace_bytes(B, N) == B * one, (B, N)
+    for N in range(257, 801):
+        one = lib.gpk_exact_grad_workspace_bytes(1, N)
+        assert one > 0, N
+        assert lib.gpk_exact_grad_workspace_bytes(5, N) == 5 * one, N
+    assert lib.gpk_exact_grad_workspace_bytes(1, 801) == 0
+    assert lib.gpk_exact_grad_workspace_bytes(4, 801) == 0
+
+
 def test_custom_ops_registered_with_fake_and_autograd():
     """The kernels are torch.library custom ops (SURVEY §8b "Who calls it"): schemas,
     FakeTensor impls (shape propagation without a GPU) and autograd formulas."""
