@@ -5,6 +5,7 @@
 #include "gpk_elbo.h"
 #include "gpk_kzz.h"
 #include "gpk_posterior_cov.h"
+#include "gpk_variational_cov_grad.h"
 
 size_t gpk_mvn_root_refine_ws_floats(int B, int n);
 int gpk_launch_mvn_root_refine(const float* cov, const float* R, int B, int n, float jitter, float* ws,
@@ -560,6 +561,72 @@ int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z
   if (B == 0) return 0;
   return var_cov_run(X, shared_x ? 0LL : (long long)B * N * D, Z, Linv, vstd, hyp, O, B, N, M, D, workspace,
                      cov, (hipStream_t)stream);
+}
+
+// ---- adjoint of the dense covariance of q(f) (gpk_variational_cov_grad.hip)
+size_t gpk_variational_cov_grad_workspace_bytes(int B, int N, int M, int D) {
+  return gpk_var_cov_grad_ws_bytes(B, N, M, D);
+}
+
+size_t gpk_variational_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_var_cov_grad_ws_bytes(B, N, M, D);
+}
+
+int gpk_variational_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
+                                 const float* hyp, const void* state, const float* gcov, int B, int N,
+                                 int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
+                                 float* dpar, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vstd == nullptr) return -4;
+  if (hyp == nullptr) return -5;
+  if (state == nullptr || ((size_t)state & 15) != 0) return -6;
+  if (gcov == nullptr) return -7;
+  if (B < 0) return -8;
+  if (N < 1 || N > kGpkMvnRootMaxN) return -9;
+  if (M < 1 || M > 256) return -10;
+  if (D < 1 || D > 64) return -11;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
+  if (dX == nullptr) return -13;
+  if (dLinv == nullptr) return -14;
+  if (dZ == nullptr) return -15;
+  if (dpar == nullptr) return -16;
+  if (B > 0 && gpk_var_cov_grad_ws_bytes(B, N, M, D) == 0) return -8;
+  if (B == 0) return 0;
+  GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, 1, 0LL, workspace,
+                      dX, dLinv, dZ, dpar};
+  return gpk_launch_var_cov_grad(a, (hipStream_t)stream);
+}
+
+int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                         const float* vstd, const float* hyp, const void* state,
+                                         const float* gcov, int O, int B, int N, int M, int D,
+                                         void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
+                                         void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vstd == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (state == nullptr || ((size_t)state & 15) != 0) return -7;
+  if (gcov == nullptr) return -8;
+  if (O < 1 || O > kGpkMaxOutputs) return -9;
+  if (B < 0) return -10;
+  if (N < 1 || N > kGpkMvnRootMaxN) return -11;
+  if (M < 1 || M > 256) return -12;
+  if (D < 1 || D > 64) return -13;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
+  if (dX == nullptr) return -15;
+  if (dLinv == nullptr) return -16;
+  if (dZ == nullptr) return -17;
+  if (dpar == nullptr) return -18;
+  if (B > 0 && gpk_var_cov_grad_ws_bytes(B, N, M, D) == 0) return -10;
+  if (B == 0) return 0;
+  GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, O,
+                      shared_x ? 0LL : (long long)B * N * D, workspace, dX, dLinv, dZ, dpar};
+  return gpk_launch_var_cov_grad(a, (hipStream_t)stream);
 }
 
 int gpk_mvn_root_max_n(void) { return kGpkMvnRootMaxN; }

@@ -662,9 +662,28 @@ def variational_dense_covariance(x, Z, Linv, vstd, outputscale, lengthscale, jit
 def _variational_cov_on_kernels(x, Z, Linv, vstd, outputscale, lengthscale) -> bool:
     """The dense covariance of q(f) runs on gpk_variational_cov_f32 when no gradient can flow
     (grad mode off, or none of the tensors requires grad) and the inputs are CUDA fp32; the
-    differentiable covariance and every CPU path stay the dense torch restatement."""
+    differentiable covariance is _variational_cov_grad_on_kernels' case, and every CPU path
+    stays the dense torch restatement."""
     return (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32 and x.numel() > 0
             and _no_grad_flows(x, Z, Linv, vstd, outputscale, lengthscale))
+
+
+def _variational_cov_grad_on_kernels(x, Z, Linv, vstd, outputscale, lengthscale) -> bool:
+    """The differentiable dense covariance of q(f) runs on gpk::variational_cov_train
+    (gpk_variational_cov_f32 keeping A, its adjoint gpk_variational_cov_grad_f32) when a gradient
+    can flow, the inputs are CUDA fp32 and the adjoint's workspace query accepts the shape
+    (M <= 256, D <= 64, N <= 256); the dense torch restatement stays for CPU tensors, other
+    dtypes and refused shapes. Z (O, M, D): the batched form, x (B, N, D) or (O, B, N, D)."""
+    if not (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32 and x.numel() > 0):
+        return False
+    if _no_grad_flows(x, Z, Linv, vstd, outputscale, lengthscale):
+        return False
+    from . import _native
+    B, N, D = x.shape[-3:]
+    M = Z.shape[-2]
+    if Z.dim() == 3:
+        return _native.lib().gpk_variational_cov_grad_batched_workspace_bytes(Z.shape[0], B, N, M, D) > 0
+    return _native.lib().gpk_variational_cov_grad_workspace_bytes(B, N, M, D) > 0
 
 
 class VariationalStrategy(nn.Module):
@@ -744,6 +763,9 @@ class VariationalStrategy(nn.Module):
         def cov():
             if _variational_cov_on_kernels(xf, Z, Linv, vstd, outputscale, lengthscale):
                 return torch.ops.gpk.variational_cov(xf, Linv, Z, vstd, hyper)
+            if _variational_cov_grad_on_kernels(xf, Z, Linv, vstd, outputscale, lengthscale):
+                return torch.ops.gpk.variational_cov_train(xf, Linv, Z, vstd, outputscale.reshape(()),
+                                                           lengthscale.reshape(-1), float(jitter))[0]
             return variational_dense_covariance(xf, Z, Linv, vstd, outputscale, lengthscale, jitter)
         return mean, var, flag, cov
 
@@ -755,8 +777,10 @@ class VariationalStrategy(nn.Module):
         expanded inputs are read in place by every output (no (O, B, N, D) copy), and the
         per-output dLinv flow into one batched K_ZZ adjoint. Returns the batch (..., O) of
         per-output q(f); the covariance is materialised on request, by the kernels
-        (gpk::variational_cov, all outputs on one launch chain) when no gradient can flow, else
-        as dense torch arithmetic from Linv[o]."""
+        (all outputs on one launch chain: gpk::variational_cov when no gradient can flow,
+        gpk::variational_cov_train with its HIP adjoint when one can; dLinv then flows into the
+        same Linv as the marginals' and the layer still runs one K_ZZ adjoint per step), and as
+        dense torch arithmetic from Linv[o] for CPU tensors, other dtypes and refused shapes."""
         from .ops_autograd import variational_predict_batched
         Z = self.inducing_points
         O, M, D = Z.shape
@@ -785,7 +809,10 @@ class VariationalStrategy(nn.Module):
             if _variational_cov_on_kernels(xk, Z, Linv, vs, s2, ls):
                 c = torch.ops.gpk.variational_cov(xk, Linv, Z, vs, hyper)       # (O, B', N, N)
                 return c.reshape(O, *batch, N, N).movedim(0, -3)
-            xo = xk.expand(O, *xk.shape) if xk.dim() == 3 else xk
+            if _variational_cov_grad_on_kernels(xk, Z, Linv, vs, s2, ls):
+                c = torch.ops.gpk.variational_cov_train(xk, Linv, Z, vs, s2, ls, float(jitter))[0]
+                return c.reshape(O, *batch, N, N).movedim(0, -3)
+            xo =xk.expand(O, *xk.shape) if xk.dim() == 3 else xk
             return torch.stack([variational_dense_covariance(xo[o], Z[o], Linv[o], vs[o], s2[o], ls[o], jitter)
                                 .reshape(*batch, N, N) for o in range(O)], dim=-3)
         return MultivariateNormal(mean.reshape(O, *batch, N).movedim(0, -2).contiguous(),

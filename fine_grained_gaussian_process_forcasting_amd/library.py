@@ -22,6 +22,10 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
                                                                                [autograd]
   gpk::variational_cov(x, Linv, Z, vstd, hyper) -> cov                        [eval only]
+  gpk::variational_cov_train(x, Linv, Z, vstd, s2, ls, jitter) -> (cov, hyper, state)
+                                                                               [autograd]
+  gpk::variational_cov_grad(x, Linv, Z, vstd, hyper, state, gcov) -> (dX, dLinv, dZ, dpar)
+      (both also for the O outputs of a multi-output layer: Z (O, M, D))
   gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [autograd]
   gpk::mvn_root_grad(R, gR, gsamples, eps) -> (dcov, dmean)
   gpk::mvn_root_refine(cov, jitter, R) -> R refined (the backward's factor when jitter > 0)
@@ -502,7 +506,7 @@ variational_elbo.register_autograd(_elbo_backward, setup_context=_elbo_setup)
 
 # ---------------------------------------------------------------------------
 # draws: dense covariance of q(f) (gpk_variational_cov_f32; no autograd formula: gp.py calls it
-# only when no gradient can flow and keeps the dense torch restatement otherwise) and the batched
+# only when no gradient can flow, and gpk::variational_cov_train below when one can) and the batched
 # Cholesky root fused with sampling (gpk_mvn_root_f32) with its adjoint (gpk_mvn_root_grad_f32).
 # ---------------------------------------------------------------------------
 
@@ -522,6 +526,99 @@ def _(x, Linv, Z, vstd, hyper):
     if Z.dim() == 3:
         return x.new_empty(Z.shape[0], B, N, N)
     return x.new_empty(B, N, N)
+
+
+# The differentiable covariance (gpk_variational_cov_f32 keeping its workspace as the saved state,
+# gpk_variational_cov_grad_f32 from it): what gp.py calls when a gradient can flow.
+
+
+def _cov_hyper(x, Z, s2, ls, jitter):
+    """The packed hyper vector gpk_variational_cov_f32 reads (s2, jitter and the lengthscales; the
+    mean's entries are not read and stay 0): (4 + 2D,), or (O, 4 + 2D) for Z (O, M, D)."""
+    D = x.shape[-1]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        return _var_hyper_batched(x, O, s2, ls, x.new_zeros(D), x.new_zeros(1), jitter)
+    return _var_hyper(x, s2, ls, x.new_zeros(D), x.new_zeros(()), jitter)
+
+
+@torch.library.custom_op("gpk::variational_cov_train", mutates_args=(), device_types="cuda")
+def variational_cov_train(x: Tensor, Linv: Tensor, Z: Tensor, vstd: Tensor, s2: Tensor, ls: Tensor,
+                          jitter: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """gpk::variational_cov from the parameters, for a gradient: -> (cov, packed hyper, state).
+    The state is the forward's workspace (A = Linv K_ZX in fp32 and the windows' means), which
+    the backward reads instead of a second fp64 product. Z (O, M, D): the batched form, with s2
+    (O,), ls (O, D) or (O, 1), vstd (O, M) and x (B, N, D) shared or (O, B, N, D)."""
+    hyper = _cov_hyper(x, Z, s2, ls, jitter)
+    if Z.dim() == 3:
+        cov, state = ops.variational_cov_batched(x, Z, Linv, vstd, hyper, return_state=True)
+    else:
+        cov, state = ops.variational_cov(x, Z, Linv, vstd, hyper, return_state=True)
+    return cov, hyper, state
+
+
+def _cov_state_numel(x, Z):
+    B, N = x.shape[-3], x.shape[-2]
+    if B == 0:
+        return 0
+    O = Z.shape[0] if Z.dim() == 3 else 1
+    return max(1, O * (_native.lib().gpk_variational_cov_workspace_bytes(B, N, Z.shape[-2]) // 4))
+
+
+@variational_cov_train.register_fake
+def _(x, Linv, Z, vstd, s2, ls, jitter):
+    B, N, D = x.shape[-3:]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        return x.new_empty(O, B, N, N), x.new_empty(O, 4 + 2 * D), x.new_empty(_cov_state_numel(x, Z))
+    return x.new_empty(B, N, N), x.new_empty(4 + 2 * D), x.new_empty(_cov_state_numel(x, Z))
+
+
+@torch.library.custom_op("gpk::variational_cov_grad", mutates_args=(), device_types="cuda")
+def variational_cov_grad(x: Tensor, Linv: Tensor, Z: Tensor, vstd: Tensor, hyper: Tensor, state: Tensor,
+                         gcov: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX, dLinv, dZ (the K_ZX part), dpar = [dvstd (M), ds2, dls (D)]); Z (O, M, D): every
+    array with a leading O, dX (O, B, N, D) per output also for shared inputs."""
+    if Z.dim() == 3:
+        return ops.variational_cov_grad_batched(x, Z, Linv, vstd, hyper, state, gcov)
+    return ops.variational_cov_grad(x, Z, Linv, vstd, hyper, state, gcov)
+
+
+@variational_cov_grad.register_fake
+def _(x, Linv, Z, vstd, hyper, state, gcov):
+    B, N, D = x.shape[-3:]
+    M = Z.shape[-2]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
+                x.new_empty(O, M + 1 + D))
+    return torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(M + 1 + D)
+
+
+def _covt_setup(ctx, inputs, output):
+    x, Linv, Z, vstd, s2, ls, jitter = inputs
+    ctx.save_for_backward(x, Linv, Z, vstd, s2, ls, output[1], output[2])
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+@torch.autograd.function.once_differentiable
+def _covt_backward(ctx, gcov, _ghyper, _gstate):
+    x, Linv, Z, vstd, s2, ls, hyper, state = ctx.saved_tensors
+    M, D = Z.shape[-2:]
+    dX, dLinv, dZ, dpar = torch.ops.gpk.variational_cov_grad(x, Linv, Z, vstd, hyper, state,
+                                                             gcov.contiguous())
+    dls = dpar[..., M + 1:]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        if x.dim() == 3:
+            dX = dX.sum(0)                      # inputs shared by the outputs
+        dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
+    else:
+        dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
+    return (dX, dLinv, dZ, dpar[..., :M].reshape(vstd.shape), dpar[..., M].reshape(s2.shape), dls, None)
+
+
+variational_cov_train.register_autograd(_covt_backward, setup_context=_covt_setup)
 
 
 @torch.library.custom_op("gpk::mvn_root", mutates_args=(), device_types="cuda")

@@ -738,12 +738,13 @@ def variational_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Te
 
 
 def variational_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
-                    hyper: torch.Tensor) -> torch.Tensor:
+                    hyper: torch.Tensor, return_state: bool = False):
     """Dense covariance of q(f) at X (B, N, D): K_XX + jitter I + A^T diag(vstd^2 - 1) A with
     A = Linv K_ZX (two gfx950 kernel launches of one C-ABI call, see
     include/gpk.h::gpk_variational_cov_f32). ``hyper`` is the variational path's packed device
     vector (pack_variational_hyper). Memory per call: the A workspace (B * M * N floats, N
-    rounded up to 64, + 64 B) lives only for the call; the result is B * N^2 floats."""
+    rounded up to 64, + 64 B) lives only for the call; the result is B * N^2 floats.
+    ``return_state``: -> (cov, workspace), the saved state ``variational_cov_grad`` runs from."""
     if X.dim() != 3:
         raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
     B, N, D = X.shape
@@ -769,21 +770,22 @@ def variational_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: 
         raise ValueError(f"gpk_variational_cov_f32 does not support B={B}, N={N}, M={M}")
     cov = torch.empty(B, N, N, device=dev, dtype=torch.float32)
     if B == 0:
-        return cov
+        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
     ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
     rc = lib.gpk_variational_cov_f32(X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(),
                                      hyper.data_ptr(), B, N, M, D, ws.data_ptr(), cov.data_ptr(),
                                      _stream_ptr(dev))
     _native.check(rc, "gpk_variational_cov_f32")
-    return cov
+    return (cov, ws) if return_state else cov
 
 
 def variational_cov_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
-                            hyper: torch.Tensor) -> torch.Tensor:
+                            hyper: torch.Tensor, return_state: bool = False):
     """``variational_cov`` for O outputs in one launch chain (gpk_variational_cov_batched_f32): X
     (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64, vstd
     (O, M), hyper (O, 4 + 2D) -> cov (O, B, N, N). Bit-identical to O single-output calls.
-    Memory per call: O workspaces of ``variational_cov`` + the O * B * N^2 floats of cov."""
+    Memory per call: O workspaces of ``variational_cov`` + the O * B * N^2 floats of cov.
+    ``return_state``: -> (cov, workspace), the saved state of ``variational_cov_grad_batched``."""
     if Z.dim() != 3:
         raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
     O, M, D = Z.shape
@@ -807,13 +809,122 @@ def variational_cov_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor
         raise ValueError(f"gpk_variational_cov_batched_f32 does not support O={O}, B={B}, N={N}, M={M}")
     cov = torch.empty(O, B, N, N, device=dev, dtype=torch.float32)
     if B == 0:
-        return cov
+        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
     ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
     rc = lib.gpk_variational_cov_batched_f32(
         X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), O, B,
         N, M, D, ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
     _native.check(rc, "gpk_variational_cov_batched_f32")
-    return cov
+    return (cov, ws) if return_state else cov
+
+
+def _cov_grad_state(state, lib, O, B, N, M, dev):
+    """The forward's workspace, as ``variational_cov(..., return_state=True)`` returned it: the C
+    entry point receives a bare pointer, so its dtype, device and size are checked here."""
+    if state.dtype != torch.float32 or state.device != dev:
+        raise ValueError(f"state must be float32 on {dev} (got {state.dtype} on {state.device}): pass "
+                         f"variational_cov(return_state=True)'s workspace unchanged")
+    want = (lib.gpk_variational_cov_workspace_bytes(B, N, M) // 4) * O
+    if state.numel() != max(1, want):
+        raise ValueError(f"state has {state.numel()} floats, this shape's forward workspace has {want}")
+    return state.detach().contiguous()
+
+
+def variational_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
+                         hyper: torch.Tensor, state: torch.Tensor, gcov: torch.Tensor):
+    """Adjoint of ``variational_cov`` (include/gpk.h::gpk_variational_cov_grad_f32, six gfx950
+    launches of one C-ABI call): from gcov (B, N, N) = dObjective / dcov and the forward's
+    workspace ``state`` returns (dX (B, N, D), dLinv (M, M) float64 lower, dZ (M, D), dpar
+    (M + 1 + D) = [dvstd, ds2, dlengthscale]). Memory per call: the workspace (2 B M N floats, N
+    rounded up to 64, + min(B, 32) M^2 doubles) lives only for the call."""
+    if X.dim() != 3:
+        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
+    B, N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape != (M, D):
+        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
+    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
+    if hyper.numel() != 4 + 2 * D:
+        raise ValueError(f"hyper must have 4 + 2D = {4 + 2 * D} entries, got {hyper.numel()}")
+    if tuple(gcov.shape) != (B, N, N):
+        raise ValueError(f"gcov must be (B, N, N) = {(B, N, N)}, got {tuple(gcov.shape)}")
+    _require_device(X, Z, Linv, vstd, hyper, state, gcov)
+    dev = X.device
+    X = X.detach().contiguous().float()
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vstd = vstd.detach().contiguous().float().reshape(-1)
+    hyper = hyper.detach().contiguous().float()
+    gcov = gcov.detach().contiguous().float()
+    if vstd.numel() != M:
+        raise ValueError(f"vstd must have M = {M} entries, got {vstd.numel()}")
+    lib = _native.lib()
+    nbytes = lib.gpk_variational_cov_grad_workspace_bytes(B, N, M, D)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_variational_cov_grad_f32 does not support B={B}, N={N}, M={M}, D={D}")
+    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(M + 1 + D, device=dev, dtype=torch.float32)
+    if B == 0:
+        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_()
+    state = _cov_grad_state(state, lib, 1, B, N, M, dev)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    rc = lib.gpk_variational_cov_grad_f32(
+        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), state.data_ptr(),
+        gcov.data_ptr(), B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(),
+        dpar.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_cov_grad_f32")
+    return dX, dLinv, dZ, dpar
+
+
+def variational_cov_grad_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
+                                 hyper: torch.Tensor, state: torch.Tensor, gcov: torch.Tensor):
+    """``variational_cov_grad`` for O outputs, every launch once
+    (gpk_variational_cov_grad_batched_f32): arguments as ``variational_cov_batched`` plus its
+    workspace ``state`` and gcov (O, B, N, N) -> (dX (O, B, N, D) per output, also with shared
+    inputs: the caller sums over O; dLinv (O, M, M) float64, dZ (O, M, D), dpar (O, M + 1 + D)).
+    Bit-identical to O single-output calls."""
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    _require_device(X, Z, Linv, vstd, hyper, state, gcov)
+    X, shared = _batched_x(X, O)
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
+    if tuple(hyper.shape) != (O, 4 + 2 * D):
+        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+    if tuple(gcov.shape) != (O, B, N, N):
+        raise ValueError(f"gcov must be (O, B, N, N) = {(O, B, N, N)}, got {tuple(gcov.shape)}")
+    dev = X.device
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vstd = vstd.detach().reshape(O, M).contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    gcov = gcov.detach().contiguous().float()
+    lib = _native.lib()
+    nbytes = lib.gpk_variational_cov_grad_batched_workspace_bytes(O, B, N, M, D)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_variational_cov_grad_batched_f32 does not support O={O}, B={B}, N={N}, "
+                         f"M={M}, D={D}")
+    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(O, M + 1 + D, device=dev, dtype=torch.float32)
+    if B == 0:
+        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_()
+    state = _cov_grad_state(state, lib, O, B, N, M, dev)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    rc = lib.gpk_variational_cov_grad_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(),
+        state.data_ptr(), gcov.data_ptr(), O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(),
+        dZ.data_ptr(), dpar.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_cov_grad_batched_f32")
+    return dX, dLinv, dZ, dpar
 
 
 MVN_ROOT_MAX_N = 256   # gpk_mvn_root_max_n(): the matrix lives in one workgroup's LDS

@@ -445,6 +445,56 @@ int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z
                                     int D, void* workspace, float* cov, void* stream);
 
 /*
+ * Adjoint of gpk_variational_cov_f32: from g = dObjective / dcov (B, N, N; any matrix, H = g + g^T
+ * is formed inside) and the forward's workspace (A = Linv K_ZX in fp32 and the windows' means of
+ * x / l, which the caller keeps as the saved state instead of a second fp64 product), with
+ * w_m = vstd_m^2 - 1:
+ *   T = A H     dvstd_m = vstd_m sum_b sum_i T_mi A_mi     dA = diag(w) T
+ *   dLinv = tril(sum_b dA K_ZX^T)                           (fp64, lower, upper triangle zero:
+ *                                                            gpk_variational_adjoint_f32's convention)
+ *   Q = (Linv^T dA) o K_ZX   and the RBF tail of K_ZX:  dZ, dX, dlengthscale, ds2
+ *   P = H o K_XX (K_ii = s2 exactly, no dX from the diagonal):  dX, dlengthscale, ds2
+ * Every difference z - x, x_i - x_j is formed from the values the forward centred (Z / l by its
+ * column means, x / l by the window's mean). The jitter has no gradient, nor has the clamp of the
+ * squared distance at 0. Linv^T dA runs on the fp32 MFMA (Linv cast on load), dLinv is accumulated
+ * on the fp64 MFMA; all partial sums are reduced in fp64 in a fixed order, no atomics: run-to-run
+ * deterministic; a window's dX depends on that window alone. Six launches on `stream`, no host
+ * synchronisation; allocates nothing and keeps no pointers.
+ *
+ * Replaces (reference): the autograd backward of upstream variational/variational_strategy.py
+ * forward's predictive_covar evaluated densely, which train.py:166 ``loss.backward()`` runs
+ * through the skip-input draw of denoising_model/DeepGP.py:62-64 ``x.rsample()``.
+ *
+ * Memory per call: the workspace, gpk_variational_cov_grad_workspace_bytes(B, N, M, D) bytes
+ * (2 B M N floats for dA and K_ZX, N rounded up to 64, min(B, 32) M^2 doubles of dLinv partials
+ * and a few KiB per workgroup of the other partials); 0 for a shape the call does not accept.
+ * The saved state is the forward's workspace: B * M * as * 4 + 256 B bytes, as = N rounded up to 64.
+ *
+ * X, Z, Linv, vstd, hyp : as gpk_variational_cov_f32   state : the workspace that call filled for
+ * the same arguments, 16-byte aligned   gcov : (B, N, N) float
+ * workspace : device memory of the size above, 16-byte aligned
+ * dX : (B, N, D) float out   dLinv : (M, M) double out   dZ : (M, D) float out (the K_ZX part)
+ * dpar : (M + 1 + D) float out = {dvstd[M], ds2, dlengthscale[D]}
+ * M <= 256, D <= 64, 1 <= N <= 256 (the bound of gpk_mvn_root_f32), B >= 0 (B = 0 launches nothing).
+ *
+ * The batched call runs O outputs with o on grid dimension y of every launch: leading dense O on
+ * Z, Linv, vstd, hyp, state (the batched forward's workspace), gcov, dLinv, dZ, dpar and dX
+ * ((O, B, N, D) also with shared inputs: the caller sums over O); the workspace is O slices of
+ * the single-output query. Output o is bit-identical to a single-output call on o's arrays.
+ */
+size_t gpk_variational_cov_grad_workspace_bytes(int B, int N, int M, int D);
+int gpk_variational_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
+                                 const float* hyp, const void* state, const float* gcov, int B, int N,
+                                 int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
+                                 float* dpar, void* stream);
+size_t gpk_variational_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D);
+int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                         const float* vstd, const float* hyp, const void* state,
+                                         const float* gcov, int O, int B, int N, int M, int D,
+                                         void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
+                                         void* stream);
+
+/*
  * Batched Cholesky root of dense covariances, fused with sampling: per matrix b
  *   R R^T = cov[b] + jitter I        (lower factor, fp32, one workgroup, the matrix in LDS)
  *   samples[s, b, i] = mean[b, i] + sum_{j <= i} R[b, i, j] eps[s, b, j]   (ascending j)
