@@ -40,6 +40,10 @@ SIGNATURES = {
     "gpk_exact_posterior_cov_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                             c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p]),
+    "gpk_exact_posterior_grad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gpk_exact_posterior_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_chol_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_double, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
@@ -112,6 +116,7 @@ SIGNATURES = {
     "gpk_mvn_root_grad_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gpk_mvn_root_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
+    "gpk_tri_solve_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gpk_mvn_root_refine_workspace_bytes": (c_size_t, [c_int, c_int]),
     "gpk_mvn_root_refine_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_void_p, c_void_p,
                                         c_void_p]),

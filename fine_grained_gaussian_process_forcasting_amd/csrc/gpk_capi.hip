@@ -5,6 +5,7 @@
 #include "gpk_elbo.h"
 #include "gpk_kzz.h"
 #include "gpk_posterior_cov.h"
+#include "gpk_posterior_grad.h"
 #include "gpk_variational_cov_grad.h"
 
 size_t gpk_mvn_root_refine_ws_floats(int B, int n);
@@ -140,6 +141,37 @@ int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, 
   if (rc != 0) return rc;
   GpkPostCovArgs c{hyp, n_lengthscale, Xs, V, mu, var, B, N, Ns, D, vs, cov};
   return gpk_launch_exact_posterior_cov(c, (hipStream_t)stream);
+}
+
+// ---- adjoint of the exact posterior (gpk_posterior_grad.hip)
+size_t gpk_exact_posterior_grad_workspace_bytes(int B, int N, int Ns, int D) {
+  return gpk_post_grad_ws_bytes(B, N, Ns, D);
+}
+
+int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                 int n_lengthscale, const float* Xs, const float* state,
+                                 const float* gmean, const float* gvar, const float* gcov,
+                                 int B, int N, int Ns, int D, void* workspace,
+                                 float* dX, float* dy, float* dXs, float* dhyp, void* stream) {
+  if (X == nullptr) return -1;
+  if (L == nullptr) return -2;
+  if (z == nullptr) return -3;
+  if (hyp == nullptr) return -4;
+  if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (Xs == nullptr) return -6;
+  if (state == nullptr || ((size_t)state & 15) != 0) return -7;   // V rows are read 16 B at a time
+  if (gmean == nullptr && gvar == nullptr && gcov == nullptr) return -8;
+  if (B < 0) return -11;
+  if (N < 1 || N > kGpkExactRegMaxN) return -12;
+  if (Ns < 1 || Ns > kGpkMvnRootMaxN) return -13;
+  if (D < 1 || D > 64) return -14;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -15;
+  if (dhyp == nullptr) return -19;
+  if (B > 0 && gpk_post_grad_ws_bytes(B, N, Ns, D) == 0) return -11;
+  if (B == 0) return 0;
+  GpkPostGradArgs a{X, L, z, hyp, n_lengthscale, Xs, state, gmean, gvar, gcov, B, N, Ns, D, workspace,
+                    dX, dy, dXs, dhyp};
+  return gpk_launch_exact_posterior_grad(a, (hipStream_t)stream);
 }
 
 int gpk_kzz_chol_f64(const float* Z, const float* hyp, int M, int D, float jitter,
@@ -644,6 +676,17 @@ int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int 
   if (info == nullptr) return -10;
   if (B == 0) return 0;
   return gpk_launch_mvn_root(cov, mean, eps, B, n, S, jitter, R, samples, info, (hipStream_t)stream);
+}
+
+int gpk_tri_solve_f32(const float* R, const float* d, int B, int n, int trans, float* w, void* stream) {
+  if (R == nullptr) return -1;
+  if (d == nullptr) return -2;
+  if (B < 0) return -3;
+  if (n < 1 || n > kGpkMvnRootMaxN) return -4;
+  if (trans != 0 && trans != 1) return -5;
+  if (w == nullptr) return -6;
+  if (B == 0) return 0;
+  return gpk_launch_tri_solve(R, d, B, n, trans, w, (hipStream_t)stream);
 }
 
 size_t gpk_mvn_root_grad_workspace_bytes(int B, int n) {

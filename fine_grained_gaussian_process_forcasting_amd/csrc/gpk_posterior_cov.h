@@ -66,6 +66,9 @@ constexpr int kGpkMvnRootMaxN = 256;
 int gpk_launch_mvn_root(const float* cov, const float* mean, const float* eps, int B, int n, int S,
                         float jitter, float* R, float* samples, int* info, hipStream_t stream);
 
+// One-right-hand-side solve against such a root (gpk_tri_solve.hip): R w = d or R^T w = d.
+int gpk_launch_tri_solve(const float* R, const float* d, int B, int n, int trans, float* w, hipStream_t stream);
+
 // Adjoint of the root and of the draws (gpk_mvn_root_grad.hip). Workspace: one packed 16 x 16
 // tile triangle per matrix, B * T (T + 1) / 2 * 256 floats with T = ceil(n / 16).
 size_t gpk_mvn_root_grad_ws_floats(int B, int n);

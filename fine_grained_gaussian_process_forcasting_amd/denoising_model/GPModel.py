@@ -12,6 +12,10 @@ parameter or the training data changes or ``train()`` is called (GPyTorch's
 ``prediction_strategy`` cache); mean and variance at x come from
 gpk_exact_posterior_f32, and the joint covariance (``covariance_matrix``, ``rsample``,
 ``log_prob``) lazily from gpk_exact_posterior_cov_f32 on the same cached factor.
+When a gradient can flow (a parameter, x or the training data requires grad), the same
+quantities come from one gpk::exact_posterior_train call on the live parameters and the
+backward is gpk_exact_posterior_grad_f32 (N <= 256 and up to 256 test points; beyond that the
+differentiable torch restatement of ``_posterior_autograd``).
 ``likelihood(model(x))`` adds the noise. As in GPyTorch,
 calling the model in eval mode on the training inputs warns (GPInputWarning) and
 returns the posterior there.
@@ -133,6 +137,8 @@ class ExactGPModel(nn.Module):
     def _posterior(self, x):
         params = [p for p in self.parameters()] + [x, self.train_inputs[0], self.train_targets]
         if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+            if self._grad_on_kernels(x):
+                return self._posterior_kernels_grad(x)
             return self._posterior_autograd(x)
         Xb, L, z, hyper = self._train_factor()
         xs = _as_batch(x).float()
@@ -157,8 +163,51 @@ class ExactGPModel(nn.Module):
 
         return MultivariateNormal(mean.reshape(shape), var.reshape(shape), covar_fn=cov)
 
+    def _grad_on_kernels(self, x) -> bool:
+        """Whether the differentiable posterior runs on the HIP kernels (gpk::exact_posterior_train,
+        backward gpk_exact_posterior_grad_f32): CUDA fp32 tensors of a shape the adjoint's workspace
+        query accepts (N <= 256, Ns <= 256, D <= 64)."""
+        train_x, train_y = self.train_inputs[0], self.train_targets
+        ts = [x, train_x, train_y] + [p for p in self.parameters()]
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in ts):
+            return False
+        Xb, xs = _as_batch(train_x), _as_batch(x)
+        if xs.shape[-1] != Xb.shape[-1] or xs.shape[0] not in (1, Xb.shape[0]):
+            return False
+        from .. import _native
+        B, N, D = Xb.shape
+        return _native.lib().gpk_exact_posterior_grad_workspace_bytes(B, N, xs.shape[1], D) > 0
+
+    def _posterior_kernels_grad(self, x):
+        """The eval posterior WITH gradients on the kernels: the factor, mean, variance and joint
+        covariance of one gpk::exact_posterior_train call on the live parameters (the packed hyper
+        vector is built differentiably, so the softplus constraints chain through torch), whose
+        backward is gpk_exact_posterior_grad_f32. The prediction cache is not used, as GPyTorch
+        does not cache through autograd either."""
+        from .. import library  # noqa: F401  (registers torch.ops.gpk)
+        train_x, train_y = self.train_inputs[0], self.train_targets
+        Xb = _as_batch(train_x)
+        yb = train_y.reshape(Xb.shape[0], Xb.shape[1])
+        xs = _as_batch(x)
+        if xs.shape[0] != Xb.shape[0]:
+            xs = xs.expand(Xb.shape[0], *xs.shape[1:])
+        kern = self.covar_module
+        # pack_exact_hyper's layout, but not detached (it detaches): dhyp must reach the parameters
+        hyper = ops.pack_exact_hyper_live(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
+                                          kern.base_kernel.lengthscale)
+        mean, var, cov, _L, _z, _state, info = torch.ops.gpk.exact_posterior_train(
+            Xb.contiguous(), yb.contiguous(), hyper, xs.contiguous(), 1e-6, 3)
+        ops.check_cholesky_info(info, 1e-6, inputs=(Xb, yb))
+        if x.dim() == 3 or Xb.shape[0] > 1:
+            shape = mean.shape
+        else:
+            shape = x.shape[:-1] if x.dim() > 1 else x.shape
+        return MultivariateNormal(mean.reshape(shape), var.reshape(shape), covar_fn=lambda: cov)
+
     def _posterior_autograd(self, x):
-        """The eval posterior WITH gradients (GPyTorch allows them; upstream
+        """The eval posterior WITH gradients where gpk_exact_posterior_grad_f32 does not reach
+        (N > 256 or more than 256 test points, other dtypes; CPU tensors raise) (GPyTorch allows
+        them; upstream
         exact_prediction_strategies.py): the same quantities as gpk_exact_posterior_f32,
         restated in differentiable torch ops on the caller's device -- K_hat = s2 RBF(X, X) +
         noise I, L = psd_safe_cholesky(K_hat) (the fp32 jitter ladder), K* = s2 RBF(X, x) over the
@@ -166,7 +215,7 @@ class ExactGPModel(nn.Module):
         z = L^{-1} (y - c), mean = c + V^T z, var = s2 - colsum(V o V). Taken only when a
         gradient will flow (a parameter, the inputs or the training data require grad): the
         prediction cache is not used, as GPyTorch does not cache through autograd either.
-        Off the hot path: no HIP kernel serves this."""
+        Off the hot path: no HIP kernel serves these shapes."""
         train_x, train_y = self.train_inputs[0], self.train_targets
         if not (x.is_cuda and train_x.is_cuda):
             raise ValueError("ExactGPModel runs on the GPU: move the model and inputs to a cuda device")

@@ -358,15 +358,23 @@ class MultivariateNormal:
         kernel. Distributions that carry a dense covariance (``covar_fn``: the exact posterior,
         variational outputs): the Gaussian log density through R = psd_safe_cholesky(Sigma),
         -0.5 (|R^{-1}(value - mean)|^2 + 2 sum log R_ii + n log 2 pi), as upstream
-        MultivariateNormal.log_prob (off the hot path: Sigma is materialised)."""
+        MultivariateNormal.log_prob (off the hot path: Sigma is materialised). Where the root is
+        the HIP one (CUDA fp32, n <= 256) the whitening solve is gpk_tri_solve_f32; elsewhere
+        torch.linalg.solve_triangular."""
         if self._exact is None and self._covar_fn is not None:
             cov = self.covariance_matrix
             root = psd_safe_cholesky(cov)
             diff = (value - self._mean).unsqueeze(-1)
             if diff.shape[:-2] != root.shape[:-2]:   # leading sample dimensions of value
                 root = root.expand(*diff.shape[:-2], *root.shape[-2:])
-            w = torch.linalg.solve_triangular(root, diff.to(root.dtype), upper=False).squeeze(-1)
             n = self._mean.shape[-1]
+            if _mvn_root_eligible(root) and diff.dtype == torch.float32 and diff.is_cuda and diff.numel() > 0:
+                # the root came from gpk_mvn_root_f32; the whitening is gpk_tri_solve_f32 (differentiable)
+                from . import library  # noqa: F401  (registers torch.ops.gpk)
+                w = torch.ops.gpk.tri_solve(root.reshape(-1, n, n).contiguous(), diff.reshape(-1, n).contiguous(),
+                                            False).reshape(diff.shape[:-1])
+            else:
+                w = torch.linalg.solve_triangular(root, diff.to(root.dtype), upper=False).squeeze(-1)
             logdet = 2.0 * root.diagonal(dim1=-2, dim2=-1).log().sum(-1)
             return -0.5 * (w.pow(2).sum(-1) + logdet + n * math.log(2.0 * math.pi))
         if self._exact is None:

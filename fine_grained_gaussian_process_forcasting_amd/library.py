@@ -10,6 +10,9 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::exact_mll_grad(X, L, z, hyper, gout) -> (dX, dy, dhyp)
   gpk::exact_posterior(X, L, z, hyper, Xs) -> (mean, var)                     [eval only]
   gpk::exact_posterior_cov(X, L, z, hyper, Xs) -> (mean, var, cov)            [eval only]
+  gpk::exact_posterior_train(X, y, hyper, Xs, jitter, max_tries)
+      -> (mean, var, cov, L, z, state, info)                                  [autograd]
+  gpk::exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov) -> (dX, dy, dXs, dhyp)
   gpk::kzz_factor(Z, s2, ls, jitter, chol_jitter, max_tries) -> (Linv, L, info) [autograd]
   gpk::variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter) -> (mean, var, flags, hyper)
                                                                                [autograd]
@@ -29,6 +32,7 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [autograd]
   gpk::mvn_root_grad(R, gR, gsamples, eps) -> (dcov, dmean)
   gpk::mvn_root_refine(cov, jitter, R) -> R refined (the backward's factor when jitter > 0)
+  gpk::tri_solve(R, d, trans) -> w with R w = d or R^T w = d (log_prob's whitening) [autograd]
 
 Reference call sites they serve: GPModel.py:10-13 + ExactMarginalLogLikelihood
 (exact_mll), ExactGPModel in eval mode (exact_posterior), DeepGP.py:33-73 VariationalStrategy (kzz_factor, variational_fwd),
@@ -105,6 +109,72 @@ def exact_posterior_cov(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor,
 def _(X, L, z, hyper, Xs):
     B, Ns, _ = Xs.shape
     return Xs.new_empty(B, Ns), Xs.new_empty(B, Ns), Xs.new_empty(B, Ns, Ns)
+
+
+# The differentiable posterior (gpk_exact_mll_f32 for the factor, gpk_exact_posterior_cov_f32 keeping
+# its workspace as the saved state, gpk_exact_posterior_grad_f32 from it): what ExactGPModel calls
+# in eval mode when a gradient can flow.
+
+
+@torch.library.custom_op("gpk::exact_posterior_train", mutates_args=(), device_types="cuda")
+def exact_posterior_train(X: Tensor, y: Tensor, hyper: Tensor, Xs: Tensor, jitter: float,
+                          max_tries: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (mean (B, Ns), var (B, Ns), cov (B, Ns, Ns), L, z, state, info): the training factor
+    from the live parameters, then the joint posterior; state is the posterior's workspace
+    (V = L^{-1} K* in fp32 and the centring mean), which the backward reads."""
+    f = ops.exact_mll(X, y, None, None, None, None, jitter=jitter, max_tries=max_tries, want_L=True,
+                      want_z=True, hyper=hyper)
+    p, state = ops.exact_posterior_cov(X, f.L, f.z, hyper, Xs, return_state=True)
+    return p.mean, p.var, p.cov, f.L, f.z, state, f.info
+
+
+def _post_state_numel(X, Xs):
+    B, N, Ns = X.shape[0], X.shape[1], Xs.shape[1]
+    return max(1, _native.lib().gpk_exact_posterior_cov_workspace_bytes(B, N, Ns) // 4)
+
+
+@exact_posterior_train.register_fake
+def _(X, y, hyper, Xs, jitter, max_tries):
+    B, N, _ = X.shape
+    Ns = Xs.shape[1]
+    return (Xs.new_empty(B, Ns), Xs.new_empty(B, Ns), Xs.new_empty(B, Ns, Ns), X.new_empty(B, N, N),
+            X.new_empty(B, N), X.new_empty(_post_state_numel(X, Xs)), X.new_empty(B, dtype=torch.int32))
+
+
+@torch.library.custom_op("gpk::exact_posterior_grad", mutates_args=(), device_types="cuda")
+def exact_posterior_grad(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor, Xs: Tensor, state: Tensor,
+                         gmean: Optional[Tensor] = None, gvar: Optional[Tensor] = None,
+                         gcov: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX (B, N, D), dy (B, N), dXs (B, Ns, D), dhyp (B, 3 + n_ls) per window)."""
+    g = ops.exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov)
+    return g.dX, g.dy, g.dXs, g.dhyp
+
+
+@exact_posterior_grad.register_fake
+def _(X, L, z, hyper, Xs, state, gmean=None, gvar=None, gcov=None):
+    B, N, D = X.shape
+    return X.new_empty(B, N, D), X.new_empty(B, N), torch.empty_like(Xs), X.new_empty(B, hyper.numel())
+
+
+def _post_train_setup(ctx, inputs, output):
+    X, y, hyper, Xs, jitter, max_tries = inputs
+    mean, var, cov, L, z, state, info = output
+    ctx.save_for_backward(X, L, z, hyper, Xs, state)
+    ctx.mark_non_differentiable(L, z, state, info)
+    ctx.set_materialize_grads(False)   # an unused mean, var or cov reaches the C entry as NULL
+
+
+@torch.autograd.function.once_differentiable
+def _post_train_backward(ctx, gmean, gvar, gcov, _gL, _gz, _gstate, _ginfo):
+    X, L, z, hyper, Xs, state = ctx.saved_tensors
+    if gmean is None and gvar is None and gcov is None:
+        return None, None, None, None, None, None
+    gmean, gvar, gcov = (g.contiguous() if g is not None else None for g in (gmean, gvar, gcov))
+    dX, dy, dXs, dhyp = torch.ops.gpk.exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov)
+    return dX, dy, dhyp.sum(0), dXs, None, None
+
+
+exact_posterior_train.register_autograd(_post_train_backward, setup_context=_post_train_setup)
 
 
 def _exact_setup(ctx, inputs, output):
@@ -661,6 +731,36 @@ def mvn_root_refine(cov: Tensor, jitter: float, R: Tensor) -> Tensor:
 @mvn_root_refine.register_fake
 def _(cov, jitter, R):
     return torch.empty_like(R)
+
+
+@torch.library.custom_op("gpk::tri_solve", mutates_args=(), device_types="cuda")
+def tri_solve(R: Tensor, d: Tensor, trans: bool) -> Tensor:
+    """w (B, n) with R w = d, or R^T w = d when trans, for lower-triangular R (B, n, n)
+    (gpk_tri_solve_f32): the whitening of MultivariateNormal.log_prob against the HIP root."""
+    return ops.tri_solve(R, d, trans)
+
+
+@tri_solve.register_fake
+def _(R, d, trans):
+    return torch.empty_like(d)
+
+
+def _tri_solve_setup(ctx, inputs, output):
+    R, d, trans = inputs
+    ctx.trans = trans
+    ctx.save_for_backward(R, output)
+
+
+def _tri_solve_backward(ctx, gw):
+    # w = op(R)^{-1} d: dd = op(R)^{-T} gw (the same kernel, transposed), d op(R) = -dd w^T, lower part
+    R, w = ctx.saved_tensors
+    gd = torch.ops.gpk.tri_solve(R, gw.contiguous(), not ctx.trans)
+    outer = gd.unsqueeze(-1) * w.unsqueeze(-2)
+    gR = -torch.tril(outer.transpose(-1, -2) if ctx.trans else outer)
+    return gR, gd, None
+
+
+tri_solve.register_autograd(_tri_solve_backward, setup_context=_tri_solve_setup)
 
 
 def _mvn_root_setup(ctx, inputs, output):

@@ -43,6 +43,14 @@ def pack_exact_hyper(outputscale, noise, mean_constant, lengthscale, device) -> 
     return torch.cat(parts).contiguous()
 
 
+def pack_exact_hyper_live(outputscale, noise, mean_constant, lengthscale) -> torch.Tensor:
+    """The same vector {s2, noise, c, lengthscale...} from tensors WITHOUT detaching them, for the
+    ops with a registered backward: their dhyp flows on to the parameters (and through the softplus
+    constraints) by torch autograd. ``pack_exact_hyper`` detaches and is for the no-grad callers."""
+    return torch.cat([outputscale.reshape(1), noise.reshape(1), mean_constant.reshape(1),
+                      lengthscale.reshape(-1)]).float()
+
+
 @dataclass
 class ExactMLLOut:
     mll: torch.Tensor            # (B,)
@@ -179,11 +187,12 @@ class ExactPosteriorCov:
 
 
 def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch.Tensor,
-                        Xs: torch.Tensor) -> ExactPosteriorCov:
+                        Xs: torch.Tensor, return_state: bool = False):
     """Joint exact-GP posterior at the test inputs ``Xs`` (B, Ns, D): ``exact_posterior``'s mean
     and variance plus the dense covariance K(xs, xs) - V^T V, V = L^{-1} K* (two gfx950 kernel
     launches of one C-ABI call, see include/gpk.h::gpk_exact_posterior_cov_f32). The V
-    workspace (B * N * Ns floats) lives only for the call."""
+    workspace (B * N * Ns floats) lives only for the call, unless ``return_state``:
+    -> (ExactPosteriorCov, workspace), the saved state ``exact_posterior_grad`` runs from."""
     if X.dim() != 3 or Xs.dim() != 3:
         raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
     B, N, D = X.shape
@@ -207,12 +216,79 @@ def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper
     var = torch.empty(B, Ns, device=dev, dtype=torch.float32)
     cov = torch.empty(B, Ns, Ns, device=dev, dtype=torch.float32)
     if B == 0 or Ns == 0:
-        return ExactPosteriorCov(mean, var, cov)
+        return (ExactPosteriorCov(mean, var, cov), ws) if return_state else ExactPosteriorCov(mean, var, cov)
     rc = lib.gpk_exact_posterior_cov_f32(
         X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), hyper.numel() - 3, Xs.data_ptr(),
         B, N, Ns, D, ws.data_ptr(), mean.data_ptr(), var.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
     _native.check(rc, "gpk_exact_posterior_cov_f32")
-    return ExactPosteriorCov(mean, var, cov)
+    return (ExactPosteriorCov(mean, var, cov), ws) if return_state else ExactPosteriorCov(mean, var, cov)
+
+
+@dataclass
+class ExactPosteriorGrad:
+    dX: Optional[torch.Tensor]    # (B, N, D)
+    dy: Optional[torch.Tensor]    # (B, N)
+    dXs: Optional[torch.Tensor]   # (B, Ns, D)
+    dhyp: torch.Tensor            # (B, 3 + n_ls): per-window d/d{s2, noise, c, lengthscale...}
+
+
+def exact_posterior_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch.Tensor,
+                         Xs: torch.Tensor, state: torch.Tensor, gmean: Optional[torch.Tensor] = None,
+                         gvar: Optional[torch.Tensor] = None, gcov: Optional[torch.Tensor] = None,
+                         want_dX: bool = True, want_dy: bool = True,
+                         want_dXs: bool = True) -> ExactPosteriorGrad:
+    """Adjoint of ``exact_posterior_cov`` (include/gpk.h::gpk_exact_posterior_grad_f32, up to six
+    gfx950 launches of one C-ABI call): from gmean (B, Ns), gvar (B, Ns) and gcov (B, Ns, Ns, any
+    matrix), each optional, and the forward's workspace ``state`` returns the gradients with
+    respect to the training inputs and targets, the test inputs and, per window, the packed
+    hyper-parameters. 1 <= N, Ns <= 256, D <= 64. The workspace lives only for the call."""
+    if X.dim() != 3 or Xs.dim() != 3:
+        raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
+    B, N, D = X.shape
+    if Xs.shape[0] != B or Xs.shape[2] != D:
+        raise ValueError(f"Xs must be (B, Ns, D) = ({B}, Ns, {D}), got {tuple(Xs.shape)}")
+    Ns = Xs.shape[1]
+    if L.shape != (B, N, N) or z.shape != (B, N):
+        raise ValueError("L / z do not match X")
+    n_ls = hyper.numel() - 3
+    if n_ls not in (1, D):
+        raise ValueError(f"hyper must have 3 + 1 or 3 + D entries, got {hyper.numel()}")
+    if gmean is None and gvar is None and gcov is None:
+        raise ValueError("at least one of gmean, gvar, gcov must be given")
+    for name, g, shape in (("gmean", gmean, (B, Ns)), ("gvar", gvar, (B, Ns)), ("gcov", gcov, (B, Ns, Ns))):
+        if g is not None and tuple(g.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
+    _require_device(X, L, z, hyper, Xs, state, *[g for g in (gmean, gvar, gcov) if g is not None])
+    dev = X.device
+    X = X.detach().contiguous().float()
+    Xs = Xs.detach().contiguous().float()
+    L = L.detach().contiguous().float()
+    z = z.detach().contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    gmean, gvar, gcov = (g.detach().contiguous().float() if g is not None else None for g in (gmean, gvar, gcov))
+    lib = _native.lib()
+    nbytes = lib.gpk_exact_posterior_grad_workspace_bytes(B, N, Ns, D)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_exact_posterior_grad_f32 does not support B={B}, N={N}, Ns={Ns}, D={D}")
+    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32) if want_dX else None
+    dy = torch.empty(B, N, device=dev, dtype=torch.float32) if want_dy else None
+    dXs = torch.empty(B, Ns, D, device=dev, dtype=torch.float32) if want_dXs else None
+    dhyp = torch.empty(B, 3 + n_ls, device=dev, dtype=torch.float32)
+    if B == 0:
+        return ExactPosteriorGrad(dX, dy, dXs, dhyp)
+    want = lib.gpk_exact_posterior_cov_workspace_bytes(B, N, Ns) // 4
+    if state.dtype != torch.float32 or state.device != dev or state.numel() != max(1, want):
+        raise ValueError(f"state must be the {want} float32 values of exact_posterior_cov(return_state=True)'s "
+                         f"workspace on {dev}, got {state.numel()} {state.dtype} on {state.device}")
+    state = state.detach().contiguous()
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    rc = lib.gpk_exact_posterior_grad_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, Xs.data_ptr(), state.data_ptr(),
+        ptr(gmean), ptr(gvar), ptr(gcov), B, N, Ns, D, ws.data_ptr(), ptr(dX), ptr(dy), ptr(dXs),
+        dhyp.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_exact_posterior_grad_f32")
+    return ExactPosteriorGrad(dX, dy, dXs, dhyp)
 
 
 INFO_TIMEOUT = 1 << 20   # gpk_exact.hip kInfoTimeout: a bounded LDS spin-wait expired
@@ -970,6 +1046,26 @@ def mvn_root(cov: torch.Tensor, jitter: float = 0.0, mean: Optional[torch.Tensor
         samples.data_ptr() if S > 0 else None, info.data_ptr(), _stream_ptr(dev))
     _native.check(rc, "gpk_mvn_root_f32")
     return R, samples, info
+
+
+def tri_solve(R: torch.Tensor, d: torch.Tensor, trans: bool = False) -> torch.Tensor:
+    """w with R w = d (or R^T w = d when ``trans``) for lower-triangular R (B, n, n) and d (B, n):
+    one gfx950 launch (include/gpk.h::gpk_tri_solve_f32), 1 <= n <= 256."""
+    if R.dim() != 3 or R.shape[-1] != R.shape[-2]:
+        raise ValueError(f"R must be (B, n, n), got {tuple(R.shape)}")
+    B, n, _ = R.shape
+    if tuple(d.shape) != (B, n):
+        raise ValueError(f"d must be (B, n) = {(B, n)}, got {tuple(d.shape)}")
+    if not 1 <= n <= MVN_ROOT_MAX_N:
+        raise ValueError(f"gpk_tri_solve_f32 takes 1 <= n <= {MVN_ROOT_MAX_N}, got n={n}")
+    _require_device(R, d)
+    R = R.detach().contiguous().float()
+    d = d.detach().contiguous().float()
+    w = torch.empty(B, n, device=R.device, dtype=torch.float32)
+    rc = _native.lib().gpk_tri_solve_f32(R.data_ptr(), d.data_ptr(), B, n, int(bool(trans)), w.data_ptr(),
+                                         _stream_ptr(R.device))
+    _native.check(rc, "gpk_tri_solve_f32")
+    return w
 
 
 def mvn_root_refine(cov: torch.Tensor, jitter: float, R: torch.Tensor) -> torch.Tensor:

@@ -141,6 +141,52 @@ int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, 
                                 void* workspace, float* mean, float* var, float* cov, void* stream);
 
 /*
+ * Adjoint of gpk_exact_posterior_cov_f32, per window b: from the gradients of the objective with
+ * respect to mean (gmean), var (gvar) and cov (gcov, ANY Ns x Ns matrix, not assumed symmetric),
+ * each optional, the gradients with respect to the training inputs and targets, the test inputs
+ * and the hyper-parameters. With G = gcov + diag(gvar), H = G + G^T, W = L^{-T} V = K_hat^{-1} K*,
+ * alpha = L^{-T} z and u = W gmean:
+ *   dK*  = -W H + alpha gmean^T       dK_hat = 1/2 W H W^T - 1/2 (u alpha^T + alpha u^T)
+ *   dK** = 1/2 H       dy = u       dc = sum gmean - sum u       dnoise = tr dK_hat
+ * and every block K = s2 E(a, b), a = x / l, gives with Q = dK o K (the diagonal of the two
+ * square blocks apart)
+ *   da_i = (Q b)_i - rowsum(Q)_i a_i      db_j = (Q^T a)_j - colsum(Q)_j b_j
+ *   dl_d = -sum (a o da + b o db)_d / l_d       ds2 = sum Q / s2 + tr dK_hat + 1/2 tr H.
+ * No Cholesky adjoint is involved; the jitter the ladder added is a constant. All three Grams are
+ * centred by the forward's training mean of x / l (read from `state`), so no difference sees the
+ * offset of the inputs. Every tile product runs on the fp32 MFMA with exact fp32 products; no
+ * atomics, fixed summation orders: a second launch gives the same bits, and the outputs of a
+ * window come from that window alone.
+ *
+ * Replaces (reference): torch autograd through upstream exact_prediction_strategies
+ * (exact_predictive_mean / exact_predictive_covar), i.e. the backward of
+ * model(x).mean / .variance / .covariance_matrix, rsample and log_prob of ExactGPModel in eval
+ * mode (denoising_model/GPModel.py:10-13) when a gradient flows.
+ *
+ * Memory per call: the workspace, gpk_exact_posterior_grad_workspace_bytes(B, N, Ns, D) bytes
+ * (W and T = W H, B * N * Ns floats each with Ns rounded up to 64; the per-column-block partials
+ * of the training side, ceil(Ns / 64) * B * N * D' floats with D' = D rounded up to 16 / 32 / 64;
+ * the gradients in scaled coordinates, B * (N + Ns) * D' floats). The query returns 0 for a shape
+ * the call does not accept: 1 <= N <= 256, 1 <= Ns <= 256 (gpk_mvn_root_max_n), 1 <= D <= 64.
+ *
+ * X, L, z, hyp, n_lengthscale, Xs : as gpk_exact_posterior_cov_f32
+ * state : the workspace of the gpk_exact_posterior_cov_f32 call on the same arguments, unchanged
+ * gmean, gvar : (B, Ns) float or NULL   gcov : (B, Ns, Ns) float or NULL; at least one is given
+ * workspace : device memory of the size above, 16-byte aligned
+ * dX : (B, N, D), dy : (B, N), dXs : (B, Ns, D) float out, each may be NULL
+ * dhyp : (B, 3 + n_lengthscale) float out, per window d/d{s2, noise, c, lengthscale...} in the
+ *        layout of gpk_exact_mll_grad_f32 (the caller sums over b)
+ * Returns -(argument index) for an invalid argument (-8 when gmean, gvar and gcov are all NULL);
+ * B == 0 returns 0 and launches nothing.
+ */
+size_t gpk_exact_posterior_grad_workspace_bytes(int B, int N, int Ns, int D);
+int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                 int n_lengthscale, const float* Xs, const float* state,
+                                 const float* gmean, const float* gvar, const float* gcov,
+                                 int B, int N, int Ns, int D, void* workspace,
+                                 float* dX, float* dy, float* dXs, float* dhyp, void* stream);
+
+/*
  * Shared inducing-point factorisation of the whitened VariationalStrategy:
  *   A    = K_ZZ + jitter (fp32 add, as K_ZZ.add_jitter), then upcast to fp64
  *   L    = psd_safe_cholesky(A) with the fp64 ladder chol_jitter * 10^t
@@ -554,6 +600,23 @@ int gpk_mvn_root_f32(const float* cov, const float* mean, const float* eps, int 
 size_t gpk_mvn_root_grad_workspace_bytes(int B, int n);
 int gpk_mvn_root_grad_f32(const float* R, const float* gR, const float* gsamples, const float* eps,
                           int B, int n, int S, void* workspace, float* dcov, float* dmean, void* stream);
+
+/*
+ * One-right-hand-side solve against a batch of lower-triangular roots, per matrix b:
+ *   trans = 0:  R w = d        trans = 1:  R^T w = d
+ * One workgroup per matrix, sixteen columns at a time: the diagonal block is solved by 16 lanes,
+ * the other rows subtract their 16 products in ascending k. fp32 FMA in a fixed order, no atomics:
+ * run-to-run deterministic. The strict upper triangle of R is not read. Allocates nothing.
+ *
+ * Replaces (reference): torch.linalg.solve_triangular in upstream distributions/
+ * multivariate_normal.py log_prob (the whitening R^{-1}(value - mean) against the root that
+ * gpk_mvn_root_f32 produced), and with trans = 1 the solve of its autograd backward
+ * (dd = R^{-T} gw, dR = -tril(dd w^T)).
+ *
+ * R : (B, n, n) float   d : (B, n) float   w : (B, n) float out (may not alias d)
+ * 1 <= n <= gpk_mvn_root_max_n() = 256, B >= 0 (B = 0 launches nothing).
+ */
+int gpk_tri_solve_f32(const float* R, const float* d, int B, int n, int trans, float* w, void* stream);
 
 /*
  * One refinement step of the fp32 root of gpk_mvn_root_f32, per matrix b:
