@@ -7,6 +7,7 @@
 #include "gpk_posterior_cov.h"
 #include "gpk_posterior_grad.h"
 #include "gpk_variational_cov_grad.h"
+#include "gpk_var_chol.h"
 
 size_t gpk_mvn_root_refine_ws_floats(int B, int n);
 int gpk_launch_mvn_root_refine(const float* cov, const float* R, int B, int n, float jitter, float* ws,
@@ -659,6 +660,77 @@ int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const flo
   GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, O,
                       shared_x ? 0LL : (long long)B * N * D, workspace, dX, dLinv, dZ, dpar};
   return gpk_launch_var_cov_grad(a, (hipStream_t)stream);
+}
+
+size_t gpk_variational_chol_saved_bytes(int B, int N, int M, int D) {
+  return gpk_var_chol_saved_bytes(B, N, M, D);
+}
+
+int gpk_variational_chol_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
+                             const float* vchol, const float* hyp, int B, int N, int M, int D, float* mean,
+                             float* var, int* flags, void* saved, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vmean == nullptr) return -4;
+  if (vchol == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (B < 0) return -7;
+  if (N < 1) return -8;
+  if (M < 1 || M > 256) return -9;
+  if (D < 1 || D > 64) return -10;
+  if (mean == nullptr) return -11;
+  if (var == nullptr) return -12;
+  if (saved != nullptr && ((size_t)saved & 15) != 0) return -14;
+  if (B == 0) return 0;
+  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved};
+  return gpk_launch_var_chol(a, (hipStream_t)stream);
+}
+
+size_t gpk_variational_chol_adjoint_workspace_bytes(int B, int N, int M, int D) {
+  return gpk_var_chol_adjoint_ws_bytes(B, N, M, D);
+}
+
+int gpk_variational_chol_adjoint_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
+                                     const float* vchol, const float* hyp, const float* gmean,
+                                     const float* gvar, const void* saved, int B, int N, int M, int D,
+                                     void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
+                                     float* dchol, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vmean == nullptr) return -4;
+  if (vchol == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (gmean == nullptr) return -7;
+  if (gvar == nullptr) return -8;
+  if (saved == nullptr || ((size_t)saved & 15) != 0) return -9;
+  if (B < 0) return -10;
+  if (N < 1 || N > 256) return -11;
+  if (M < 1 || M > 256) return -12;
+  if (D < 1 || D > 64) return -13;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
+  if (dX == nullptr) return -15;
+  if (dLinv == nullptr) return -16;
+  if (dZ == nullptr) return -17;
+  if (dpar == nullptr) return -18;
+  if (dchol == nullptr) return -19;
+  if (B > 0 && gpk_var_chol_adjoint_ws_bytes(B, N, M, D) == 0) return -10;
+  if (B == 0) return 0;
+  GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
+                      dX, dLinv, dZ, dpar, dchol};
+  return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
+}
+
+int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,
+                        float* dchol, void* stream) {
+  if (m == nullptr) return -1;
+  if (chol == nullptr) return -2;
+  if (M < 1 || M > 16384) return -3;
+  if (gkl == nullptr && kl == nullptr) return -4;
+  if (gkl != nullptr && dm == nullptr) return -6;
+  if (gkl != nullptr && dchol == nullptr) return -7;
+  return gpk_launch_chol_kl(m, chol, M, kl, gkl, dm, dchol, (hipStream_t)stream);
 }
 
 int gpk_mvn_root_max_n(void) { return kGpkMvnRootMaxN; }

@@ -24,3 +24,12 @@ struct GpkVarCovGradArgs {
 // 0 for a shape the kernels do not take.
 size_t gpk_var_cov_grad_ws_bytes(int B, int N, int M, int D);
 int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream);
+
+// The part of the pipeline that runs from a dA the caller has materialised in the workspace
+// (row-major (B, M, as) floats at *off_dA bytes into it): q, dlinv, reduce, finish -- no t, no
+// kxx, for an objective that has no K_XX term (the Cholesky q(u) adjoint, gpk_var_chol.hip).
+// Same kernels, same workspace plan (the query returns the plan's size, 0 for a refused shape);
+// state and gcov are not read, the dw and kxx partials are zero-filled so that dpar[0..M) comes
+// out 0 and ds2 / dlengthscale carry the K_ZX part alone; vstd only needs to be readable.
+size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, int* as);
+int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, hipStream_t stream);

@@ -781,7 +781,7 @@ size_t gpk_var_cov_grad_ws_bytes(int B, int N, int M, int D) {
   return vcg_plan(B, N, M, D).total;
 }
 
-int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream) {
+static void vcg_set_lds_once() {
   static std::once_flag once;
   std::call_once(once, [] {
     (void)hipFuncSetAttribute((const void*)gpk_vcg_q_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -789,6 +789,39 @@ int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream) {
     (void)hipFuncSetAttribute((const void*)gpk_vcg_q_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipGetLastError();
   });
+}
+
+size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, int* as) {
+  if (!vcg_shape_ok(B, N, M, D)) return 0;
+  const VcgPlan p = vcg_plan(B, N, M, D);
+  if (off_dA != nullptr) *off_dA = p.off_dA;
+  if (as != nullptr) *as = p.as;
+  return p.total;
+}
+
+int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, hipStream_t stream) {
+  vcg_set_lds_once();
+  if (!vcg_shape_ok(a.B, a.N, a.M, a.D) || a.O != 1) return -9;
+  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0};
+  const unsigned gq = (unsigned)(k.p.nchunk * k.p.ncb);
+  const size_t lds = vcg_q_lds(k.p.MP, k.p.Dq);
+  const long long nred = ((long long)a.M * a.M + (long long)k.p.MP * k.p.Dq + 255) / 256;
+  // what t and kxx would have written: no dw, no K_XX partials
+  hipError_t e = hipMemsetAsync((char*)a.ws + k.p.off_dw, 0, (size_t)a.B * a.M * sizeof(float), stream);
+  if (e == hipSuccess)
+    e = hipMemsetAsync((char*)a.ws + k.p.off_cp, 0, (size_t)gq * 128 * sizeof(float), stream);
+  if (e != hipSuccess) return (int)e;
+  if (k.p.Dq == 16) hipLaunchKernelGGL(gpk_vcg_q_kernel<1>, dim3(gq, 1), dim3(256), lds, stream, k);
+  else if (k.p.Dq == 32) hipLaunchKernelGGL(gpk_vcg_q_kernel<2>, dim3(gq, 1), dim3(256), lds, stream, k);
+  else hipLaunchKernelGGL(gpk_vcg_q_kernel<4>, dim3(gq, 1), dim3(256), lds, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_dlinv_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit), 1), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_reduce_kernel, dim3((unsigned)nred, 1), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_finish_kernel, dim3(1, 1), dim3(256), 0, stream, k);
+  return (int)hipGetLastError();
+}
+
+int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream) {
+  vcg_set_lds_once();
   if (!vcg_shape_ok(a.B, a.N, a.M, a.D)) return -9;
   VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0};
   k.state_stride = (long long)a.B * a.M * k.p.as + (long long)a.B * 64;

@@ -12,6 +12,7 @@ train.py:20) read the same and its state_dicts keep their keys:
   GaussianLikelihood                     gpytorch.likelihoods (noise_covar.raw_noise)
   MultivariateNormal                     gpytorch.distributions (mean, variance clamp)
   MeanFieldVariationalDistribution       gpytorch.variational
+  CholeskyVariationalDistribution        gpytorch.variational (chol_variational_covar)
   VariationalStrategy                    gpytorch.variational (whitened)
   VariationalELBO / DeepApproximateMLL   gpytorch.mlls
   ExactMarginalLogLikelihood             gpytorch.mlls
@@ -647,6 +648,90 @@ class MeanFieldVariationalDistribution(nn.Module):
         return 0.5 * (s2.sum(-1) + m.pow(2).sum(-1) - m.shape[-1] - s2.log().sum(-1))
 
 
+class CholeskyVariationalDistribution(nn.Module):
+    """q(u) = N(m, L_q L_q^T), L_q = tril(chol_variational_covar): upstream
+    variational/cholesky_variational_distribution.py (GPyTorch's default distribution). The
+    strict upper triangle of the parameter is never read and gets exactly zero gradient; its
+    diagonal is unconstrained (a negative entry is legal: the covariance and the log-determinant
+    see its square)."""
+
+    def __init__(self, num_inducing_points: int, batch_shape=torch.Size([]), mean_init_std=1e-3):
+        super().__init__()
+        self.num_inducing_points = num_inducing_points
+        self.mean_init_std = mean_init_std
+        mean_init = torch.zeros(num_inducing_points).repeat(*batch_shape, 1)
+        covar_init = torch.eye(num_inducing_points, num_inducing_points).repeat(*batch_shape, 1, 1)
+        self.register_parameter("variational_mean", nn.Parameter(mean_init))
+        self.register_parameter("chol_variational_covar", nn.Parameter(covar_init))
+
+    def initialize_variational_distribution(self):
+        # prior N(0, I) (whitened): m = 0 + mean_init_std * randn, L_q = I
+        with torch.no_grad():
+            self.variational_mean.data.zero_()
+            self.variational_mean.data.add_(torch.randn_like(self.variational_mean), alpha=self.mean_init_std)
+            C = self.chol_variational_covar.data
+            C.zero_()
+            C.diagonal(dim1=-2, dim2=-1).fill_(1.0)
+
+    def kl_divergence(self) -> torch.Tensor:
+        """KL(q || N(0, I)) = 1/2 (|L_q|_F^2 + |m|^2 - M - sum_k log L_q,kk^2): one gfx950 launch
+        each way (gpk::cholesky_kl) for the unbatched CUDA fp32 layer, the closed form in torch
+        elsewhere."""
+        m = self.variational_mean
+        C = self.chol_variational_covar
+        if m.is_cuda and m.dim() == 1 and m.dtype == torch.float32 and C.dtype == torch.float32:
+            return torch.ops.gpk.cholesky_kl(m, C).reshape(())
+        return cholesky_kl_closed_form(m, C)
+
+
+def cholesky_kl_closed_form(m, C):
+    """KL(N(m, L L^T) || N(0, I)) with L = tril(C), batched over leading dimensions (torch)."""
+    L = torch.tril(C)
+    logdet = L.diagonal(dim1=-2, dim2=-1).pow(2).log().sum(-1)
+    return 0.5 * (L.pow(2).sum((-1, -2)) + m.pow(2).sum(-1) - m.shape[-1] - logdet)
+
+
+def _variational_interp(x, Z, Linv, outputscale, lengthscale):
+    """A = L^{-1} K_ZX (B', M, N) as upstream's whitened strategy forms it: the solve in fp64,
+    cast back to the dtype of x."""
+    ls = lengthscale.reshape(-1)
+    s2 = outputscale.reshape(())
+    zs = (Z / ls).double()
+    xs = (x / ls).double()
+    d = (zs.pow(2).sum(-1)[:, None] + xs.pow(2).sum(-1).unsqueeze(-2)
+         - 2.0 * zs @ xs.transpose(-1, -2)).clamp_min(0.0)             # (B', M, N)
+    Kzx = s2.double() * torch.exp(-0.5 * d)
+    return (Linv.double() @ Kzx).to(x.dtype)
+
+
+def variational_chol_predict(x, Z, Linv, vmean, vchol, outputscale, lengthscale, weights, bias, jitter):
+    """(mean, unclamped variance) of q(f) at x (B', N, D) for the whitened strategy with a Cholesky
+    q(u) = N(vmean, L_q L_q^T), L_q = tril(vchol), written out in differentiable torch:
+      A = Linv K_ZX   W = L_q^T A   mean = A^T m + x w + b0   var = s2 + jitter - sum A^2 + sum W^2
+    The formulas of gpk_variational_chol_f32 / its adjoint: the fallback for shapes the kernels
+    refuse and for multi-output layers, and the tests' fp64 reference. ``weights`` (D,) or None."""
+    A = _variational_interp(x, Z, Linv, outputscale, lengthscale)
+    Lq = torch.tril(vchol).to(x.dtype)
+    W = Lq.transpose(-1, -2) @ A
+    mean = (A * vmean.reshape(-1).to(x.dtype)[:, None]).sum(-2) + bias
+    if weights is not None:
+        mean = mean + x @ weights.reshape(-1).to(x.dtype)
+    var = outputscale.reshape(()) + jitter - A.pow(2).sum(-2) + W.pow(2).sum(-2)
+    return mean, var
+
+
+def variational_chol_dense_covariance(x, Z, Linv, vchol, outputscale, lengthscale, jitter):
+    """The full predictive covariance K_XX + jitter I + W^T W - A^T A of q(f) with a Cholesky q(u)
+    (dense torch arithmetic, on request: covariance_matrix / rsample)."""
+    ls = lengthscale.reshape(-1)
+    s2 = outputscale.reshape(())
+    A = _variational_interp(x, Z, Linv, s2, ls)
+    W = torch.tril(vchol).to(x.dtype).transpose(-1, -2) @ A
+    eye = torch.eye(x.shape[-2], dtype=x.dtype, device=x.device)
+    return (rbf_covariance(x, ls, s2) + jitter * eye + W.transpose(-1, -2) @ W
+            - A.transpose(-1, -2) @ A)
+
+
 def variational_dense_covariance(x, Z, Linv, vstd, outputscale, lengthscale, jitter):
     """The full predictive covariance of q(f) at x (B', N, D), as upstream
     VariationalStrategy.forward (whitened) builds it lazily: K_XX + jitter I + A^T (S - I) A with
@@ -744,6 +829,8 @@ class VariationalStrategy(nn.Module):
             self._variational_distribution.initialize_variational_distribution()
             self.variational_params_initialized.fill_(1)
             self._initialized = True
+        if isinstance(self._variational_distribution, CholeskyVariationalDistribution):
+            return self._call_chol(x)
         if self.inducing_points.dim() == 3:
             return self._call_batched(x)
         model = self.model
@@ -776,6 +863,73 @@ class VariationalStrategy(nn.Module):
                                                            lengthscale.reshape(-1), float(jitter))[0]
             return variational_dense_covariance(xf, Z, Linv, vstd, outputscale, lengthscale, jitter)
         return mean, var, flag, cov
+
+    def _call_chol(self, x: torch.Tensor) -> MultivariateNormal:
+        """q(f) with a CholeskyVariationalDistribution. One output, CUDA fp32 inputs and a shape the
+        kernels' queries accept (M <= 256, D <= 64; N <= 256 when a gradient can flow):
+        ops_autograd.variational_predict_chol (gpk_variational_chol_f32 and its HIP adjoint). Every
+        other case -- a refused shape, another dtype, a multi-output layer (inducing points
+        (O, M, D), one torch evaluation per output) -- is variational_chol_predict in torch from the
+        same shared K_ZZ factor (KzzCache); the dense covariance behind covariance_matrix / rsample
+        is torch in every case."""
+        from .ops_autograd import _mean_params, _mean_params_batched, variational_predict_chol
+        model = self.model
+        kern = model.covar_module
+        q = self._variational_distribution
+        Z = self.inducing_points
+        jitter = self._jitter(x.dtype)
+        key = (Z, kern.raw_outputscale, kern.base_kernel.raw_lengthscale)
+        N, D = x.shape[-2:]
+        if Z.dim() == 3:
+            O, M, _ = Z.shape
+            if x.dim() < 3 or x.shape[-3] != O:
+                raise RuntimeError(f"a layer with {O} outputs takes inputs (..., {O}, N, D); got {tuple(x.shape)}")
+            batch = x.shape[:-3]
+            s2 = kern.outputscale.reshape(O)
+            ls = kern.base_kernel.lengthscale.reshape(O, -1)
+            Linv = self._kzz_cache.factor(Z, s2, ls, jitter, key)
+            w, b0 = _mean_params_batched(model.mean_module, O, D, x.device)
+            xo = x.movedim(-3, 0).reshape(O, -1, N, D)
+            vm, vc = q.variational_mean.reshape(O, M), q.chol_variational_covar.reshape(O, M, M)
+            outs = [variational_chol_predict(xo[o], Z[o], Linv[o], vm[o], vc[o], s2[o], ls[o],
+                                             w[o] if w.dim() == 2 else w, b0[o] if b0.numel() == O else b0[0],
+                                             jitter) for o in range(O)]
+            mean = torch.stack([m for m, _ in outs]).reshape(O, *batch, N).movedim(0, -2)
+            var = torch.stack([v for _, v in outs]).reshape(O, *batch, N).movedim(0, -2)
+            self._kzz_cache.note_consumers(mean, var)
+            self._kzz_cache.check_pending()
+
+            def cov():
+                return torch.stack([variational_chol_dense_covariance(xo[o], Z[o], Linv[o], vc[o], s2[o], ls[o],
+                                                                      jitter).reshape(*batch, N, N)
+                                    for o in range(O)], dim=-3)
+            return MultivariateNormal(mean.contiguous(), var.contiguous(), covar_fn=cov)
+
+        batch = x.shape[:-2]
+        M = Z.shape[0]
+        xf = x.reshape(-1, N, D)
+        s2, ls = kern.outputscale, kern.base_kernel.lengthscale
+        vm, vc = q.variational_mean, q.chol_variational_covar
+        grad = torch.is_grad_enabled()
+        on_kernels = (xf.is_cuda and xf.dtype == torch.float32 and Z.dtype == torch.float32
+                      and vc.dtype == torch.float32
+                      and ops.variational_chol_supported(xf.shape[0], N, M, D, adjoint=grad))
+        if on_kernels:
+            mean, var, flag, Linv = variational_predict_chol(
+                xf, Z, vm, vc, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
+                return_linv=True)
+        else:
+            Linv = self._kzz_cache.factor(Z, s2.reshape(()), ls.reshape(-1), jitter, key)
+            w, b0 = _mean_params(model.mean_module, D, x.device)
+            mean, var = variational_chol_predict(xf, Z, Linv, vm, vc, s2, ls, w, b0, jitter)
+            flag = None
+            self._kzz_cache.note_consumers(mean, var)
+            self._kzz_cache.check_pending()
+
+        def cov():
+            return variational_chol_dense_covariance(xf, Z, Linv, vc, s2, ls, jitter).reshape(*batch, N, N)
+        return MultivariateNormal(mean.reshape(*batch, N), var.reshape(*batch, N), clamp_flag=flag,
+                                  covar_fn=cov)
 
     def _call_batched(self, x: torch.Tensor) -> MultivariateNormal:
         """Multi-output layer (output_dims = O, DeepGP.py:24-26): inducing points (O, M, D), q(u)

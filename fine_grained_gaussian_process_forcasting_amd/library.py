@@ -20,6 +20,11 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::kzz_factor_batched / gpk::variational_fwd_batched / gpk::variational_adj_batched
       the three ops above for the O output GPs of a multi-output layer (leading O on every
       array, the inputs shared or per output), one launch chain for all outputs    [autograd]
+  gpk::variational_chol_fwd(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save)
+      -> (mean, var, flags, hyper, saved): q(u) = N(vmean, tril(vchol) tril(vchol)^T)    [autograd]
+  gpk::variational_chol_adj(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved)
+      -> (dX, dLinv, dZ, dpar, dchol)
+  gpk::cholesky_kl(m, chol) -> kl (1,)                                        [autograd]
   gpk::gauss_ell(y, mean, var, noise) -> ell (R,)                             [autograd]
   gpk::meanfield_kl(m, s) -> kl (1,)                                          [autograd]
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
@@ -801,3 +806,118 @@ def _mvn_root_backward(ctx, gR, gsamples, _ginfo):
 
 
 mvn_root.register_autograd(_mvn_root_backward, setup_context=_mvn_root_setup)
+
+# ---------------------------------------------------------------------------
+# Cholesky (full-covariance) q(u): gpk_variational_chol_f32 / gpk_variational_chol_adjoint_f32 /
+# gpk_cholesky_kl_f32 (upstream CholeskyVariationalDistribution inside VariationalStrategy)
+# ---------------------------------------------------------------------------
+
+
+def _chol_saved_numel(x, Z, save):
+    if not save or x.shape[0] < 1:
+        return 0
+    B, N, D = x.shape
+    return _native.lib().gpk_variational_chol_saved_bytes(B, N, Z.shape[0], D) // 4
+
+
+@torch.library.custom_op("gpk::variational_chol_fwd", mutates_args=(), device_types="cuda")
+def variational_chol_fwd(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor, s2: Tensor,
+                         ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
+                         save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (mean, var, clamp flags, packed hyper vector, saved state): gpk::variational_fwd with
+    q(u) = N(vmean, tril(vchol) tril(vchol)^T). ``save`` (a gradient will be needed): the forward
+    keeps A = Linv K_ZX and the clamp mask, which the adjoint reads; else the state is empty."""
+    hyper = _var_hyper(x, s2, ls, w, b0, jitter)
+    out = ops.variational_chol_forward(x, Z, Linv, vmean, vchol, hyper, save=save)
+    saved = out.saved if out.saved is not None else x.new_empty(0)
+    return out.mean, out.var, out.flags, hyper, saved
+
+
+@variational_chol_fwd.register_fake
+def _(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save=False):
+    B, N, D = x.shape
+    return (x.new_empty(B, N), x.new_empty(B, N), x.new_empty(1, dtype=torch.int32),
+            x.new_empty(4 + 2 * D), x.new_empty(_chol_saved_numel(x, Z, save)))
+
+
+@torch.library.custom_op("gpk::variational_chol_adj", mutates_args=(), device_types="cuda")
+def variational_chol_adj(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor, hyper: Tensor,
+                         gmean: Tensor, gvar: Tensor,
+                         saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX, dLinv, dZ (K_ZX part), dpar = [dvmean (M), ds2, dls (D), dw (D), db0], dchol (M, M)
+    lower) from the forward's ``saved`` state."""
+    return ops.variational_chol_adjoint(x, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+
+
+@variational_chol_adj.register_fake
+def _(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved):
+    M, D = Z.shape
+    return (torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(M + 2 * D + 2),
+            x.new_empty(M, M))
+
+
+def _vchol_setup(ctx, inputs, output):
+    x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter = inputs[:10]
+    ctx.save_for_backward(x, Linv, Z, vmean, vchol, s2, ls, w, b0, output[3], output[4])
+    ctx.mark_non_differentiable(output[2], output[3], output[4])
+
+
+def _vchol_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
+    x, Linv, Z, vmean, vchol, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
+    B, N, D = x.shape
+    M = Z.shape[0]
+    if saved.numel() == 0 and B > 0:
+        raise RuntimeError("gpk::variational_chol_fwd was called with save=False; no backward")
+    if gmean is None:
+        gmean = x.new_zeros(B, N)
+    if gvar is None:
+        gvar = x.new_zeros(B, N)
+    if B == 0:
+        dX, dLinv, dZ = torch.zeros_like(x), torch.zeros_like(Linv), torch.zeros_like(Z)
+        dpar, dchol = x.new_zeros(M + 2 * D + 2), x.new_zeros(M, M)
+    else:
+        dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_adj(
+            x, Linv, Z, vmean, vchol, hyper, gmean.contiguous(), gvar.contiguous(), saved)
+    dls = dpar[M + 1:M + 1 + D]
+    dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
+    return (dX, dLinv, dZ, dpar[:M].reshape(vmean.shape), dchol.reshape(vchol.shape), dpar[M].reshape(s2.shape),
+            dls, dpar[M + 1 + D:M + 1 + 2 * D].reshape(w.shape), dpar[M + 1 + 2 * D].reshape(b0.shape),
+            None, None)
+
+
+variational_chol_fwd.register_autograd(_vchol_backward, setup_context=_vchol_setup)
+
+
+@torch.library.custom_op("gpk::cholesky_kl", mutates_args=(), device_types="cuda")
+def cholesky_kl(m: Tensor, chol: Tensor) -> Tensor:
+    """(1,) KL(N(m, L L^T) || N(0, I)), L = tril(chol), of the whitened Cholesky q(u)."""
+    return ops.cholesky_kl(m.contiguous().float(), chol.contiguous().float())
+
+
+@cholesky_kl.register_fake
+def _(m, chol):
+    return m.new_empty(1)
+
+
+@torch.library.custom_op("gpk::cholesky_kl_grad", mutates_args=(), device_types="cuda")
+def cholesky_kl_grad(m: Tensor, chol: Tensor, gkl: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.cholesky_kl_grad(m.contiguous().float(), chol.contiguous().float(),
+                                gkl.reshape(1).contiguous().float())
+
+
+@cholesky_kl_grad.register_fake
+def _(m, chol, gkl):
+    return torch.empty_like(m), torch.empty_like(chol)
+
+
+def _ckl_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _ckl_backward(ctx, gkl):
+    m, chol = ctx.saved_tensors
+    dm, dchol = torch.ops.gpk.cholesky_kl_grad(m, chol, gkl)
+    return dm, dchol
+
+
+cholesky_kl.register_autograd(_ckl_backward, setup_context=_ckl_setup)

@@ -1299,3 +1299,126 @@ def variational_elbo_grad(y, mean, var, noise, vmean, vstd, kl_scale: float, gel
                                                      ds.data_ptr(), _stream_ptr(dev))
     _native.check(rc, "gpk_variational_elbo_grad_f32")
     return dmean, dvar, part.sum().reshape(1), dm, ds
+
+
+# ---------------------------------------------------------------------------
+# Cholesky (full-covariance) q(u): gpk_variational_chol_f32 / _adjoint_f32, gpk_cholesky_kl_f32
+# ---------------------------------------------------------------------------
+def variational_chol_supported(B: int, N: int, M: int, D: int, adjoint: bool = False) -> bool:
+    """Whether the Cholesky-q(u) kernels serve the shape (the *_bytes queries of include/gpk.h:
+    forward M <= 256, D <= 64; the adjoint additionally N <= 256)."""
+    if B < 1:
+        return False
+    lib = _native.lib()
+    if adjoint:
+        return lib.gpk_variational_chol_adjoint_workspace_bytes(B, N, M, D) > 0
+    return lib.gpk_variational_chol_saved_bytes(B, N, M, D) > 0
+
+
+@dataclass
+class VariationalCholOut:
+    mean: torch.Tensor             # (B, N)
+    var: torch.Tensor              # (B, N) clamped at 1e-6
+    flags: Optional[torch.Tensor]  # (1,) int32: bit 0 = the variance clamp fired
+    saved: Optional[torch.Tensor]  # A = Linv K_ZX (B, M, as) and the clamp mask (B, as), or None
+
+
+def variational_chol_forward(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                             vchol: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
+                             save: bool = False) -> VariationalCholOut:
+    """Batched q(f) mean / variance of the whitened VariationalStrategy with a Cholesky q(u)
+    (include/gpk.h::gpk_variational_chol_f32); ``hyper`` is pack_variational_hyper's vector.
+    ``save=True`` keeps A and the clamp mask for ``variational_chol_adjoint``."""
+    if X.dim() != 3:
+        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
+    B, N, D = X.shape
+    M = Z.shape[0]
+    if Z.shape != (M, D):
+        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
+    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
+    if vchol.shape != (M, M):
+        raise ValueError(f"chol_variational_covar must be ({M}, {M}), got {tuple(vchol.shape)}")
+    _require_device(X, Z, Linv, vmean, vchol, hyper)
+    dev = X.device
+    X = X.detach().contiguous().float()
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous()
+    vmean = vmean.detach().contiguous().float().reshape(-1)
+    vchol = vchol.detach().contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    mean = torch.empty(B, N, device=dev, dtype=torch.float32)
+    var = torch.empty(B, N, device=dev, dtype=torch.float32)
+    flags = torch.zeros(1, device=dev, dtype=torch.int32) if want_flags else None
+    lib = _native.lib()
+    saved = None
+    if B > 0:
+        nsaved = lib.gpk_variational_chol_saved_bytes(B, N, M, D)
+        if nsaved == 0:
+            raise ValueError(f"gpk_variational_chol_f32 does not support B={B}, N={N}, M={M}, D={D}")
+        if save:
+            saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_chol_f32(
+        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
+        B, N, M, D, mean.data_ptr(), var.data_ptr(), flags.data_ptr() if flags is not None else None,
+        saved.data_ptr() if saved is not None else None, _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_f32")
+    return VariationalCholOut(mean, var, flags, saved)
+
+
+def variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
+    """Adjoint of ``variational_chol_forward`` except the shared K_ZZ factor
+    (include/gpk.h::gpk_variational_chol_adjoint_f32) -> (dX (B, N, D), dLinv (M, M) float64 lower,
+    dZ (M, D), dpar (M + 2D + 2) = [dvmean, ds2, dls, dw, db0], dchol (M, M) lower)."""
+    B, N, D = X.shape
+    M = Z.shape[0]
+    _require_device(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+    dev = X.device
+    lib = _native.lib()
+    if saved.dtype != torch.float32 or saved.device != dev:
+        raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device})")
+    if saved.numel() * 4 != lib.gpk_variational_chol_saved_bytes(B, N, M, D):
+        raise ValueError("saved state does not match this shape (variational_chol_forward(save=True))")
+    nbytes = lib.gpk_variational_chol_adjoint_workspace_bytes(B, N, M, D)
+    if nbytes == 0:
+        raise ValueError(f"gpk_variational_chol_adjoint_f32 does not support B={B}, N={N}, M={M}, D={D}")
+    X = X.detach().contiguous().float()
+    Z = Z.detach().contiguous().float()
+    Linv = Linv.detach().contiguous().double()
+    vmean = vmean.detach().reshape(M).contiguous().float()
+    vchol = vchol.detach().contiguous().float()
+    hyper = hyper.detach().contiguous().float()
+    gmean = gmean.detach().reshape(B, N).contiguous().float()
+    gvar = gvar.detach().reshape(B, N).contiguous().float()
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(M + 2 * D + 2, device=dev, dtype=torch.float32)
+    dchol = torch.empty(M, M, device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_chol_adjoint_f32(
+        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
+        gmean.data_ptr(), gvar.data_ptr(), saved.detach().contiguous().data_ptr(), B, N, M, D, ws.data_ptr(),
+        dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_adjoint_f32")
+    return dX, dLinv, dZ, dpar, dchol
+
+
+def cholesky_kl(m: torch.Tensor, chol: torch.Tensor) -> torch.Tensor:
+    """KL(N(m, L L^T) || N(0, I)), L = tril(chol), as a (1,) tensor (one launch)."""
+    _require_device(m, chol)
+    kl = torch.empty(1, device=m.device, dtype=torch.float32)
+    rc = _native.lib().gpk_cholesky_kl_f32(m.data_ptr(), chol.data_ptr(), m.numel(), kl.data_ptr(), None, None,
+                                           None, _stream_ptr(m.device))
+    _native.check(rc, "gpk_cholesky_kl_f32")
+    return kl
+
+
+def cholesky_kl_grad(m, chol, gkl):
+    _require_device(m, chol, gkl)
+    dm = torch.empty_like(m)
+    dchol = torch.empty_like(chol)
+    rc = _native.lib().gpk_cholesky_kl_f32(m.data_ptr(), chol.data_ptr(), m.numel(), None, gkl.data_ptr(),
+                                           dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
+    _native.check(rc, "gpk_cholesky_kl_f32")
+    return dm, dchol

@@ -162,6 +162,30 @@ def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module
     return out
 
 
+def variational_predict_chol(x, Z, vmean, vchol, outputscale, lengthscale, mean_module, jitter,
+                             cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
+    """``variational_predict`` for a Cholesky q(u) = N(vmean, L_q L_q^T), L_q = tril(vchol)
+    (gpk::variational_chol_fwd, HIP forward and backward): the same shared K_ZZ factor, spent-marking
+    and pending psd_safe_cholesky verdict. The caller has checked that the kernels serve the shape
+    (ops.variational_chol_supported)."""
+    w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
+    s2 = outputscale.reshape(())
+    ls = lengthscale.reshape(-1)
+    if cache is None or key_tensors is None:
+        cache = KzzCache()
+        key_tensors = (Z, s2, ls)
+    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vchol, s2, ls, w, b0))
+    mean, var, flags, _, _ = torch.ops.gpk.variational_chol_fwd(x, Linv, Z, vmean, vchol, s2, ls, w, b0,
+                                                                float(jitter), save)
+    cache.note_consumers(mean, var)
+    cache.check_pending()
+    out = (mean, var, flags)
+    if return_linv:
+        out += (Linv,)
+    return out
+
+
 def _mean_params_batched(mean_module, O, D, device):
     """(w, b0) of a multi-output layer's mean (DeepGP.py:42-45): ConstantMean(batch_shape=[O])
     as w = 0, b0 (O,) (one gradient per output); LinearMean with weights (O, D, 1) per output,

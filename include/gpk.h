@@ -541,6 +541,67 @@ int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const flo
                                          void* stream);
 
 /*
+ * Variational predictive distribution with a Cholesky (full-covariance) q(u) = N(m, L_q L_q^T),
+ * whitened (prior N(0, I)), L_q = tril(C) of the parameter C = chol_variational_covar: the strict
+ * upper triangle of C is never read, its diagonal may be negative. Per window b:
+ *   K_ZX, A = Linv K_ZX                              exactly as gpk_variational_f32 (fp64, cast to fp32)
+ *   W    = L_q^T A                                   (M, N), fp32 MFMA
+ *   mean = A^T m + x @ w + b0
+ *   var  = max(s2 + jitter - sum_m A_mi^2 + sum_m W_mi^2, 1e-6)      flags bit 0: the clamp fired
+ * and the adjoint for the objective sum(gmean * mean) + sum(gvar * var), gvar zeroed where the
+ * clamp fired, everything but the K_ZZ factor:
+ *   dA = gmean_i m + 2 gvar_i (L_q w_i - a_i)        dvmean = sum_{b,i} gmean_i a_i
+ *   dchol = 2 tril(sum_{b,i} gvar_i a_i w_i^T)       (M, M) float, lower, upper triangle zero
+ *   dLinv = tril(sum dA K_ZX^T) (fp64, lower, upper zero), Q = (Linv^T dA) o K_ZX and the RBF tail
+ *   dX (RBF adjoint + gmean_i w), dZ (the K_ZX part), dl, ds2 (K_ZX part + sum of the unclamped
+ *   gvar), dweights = X^T gmean, dbias = sum gmean
+ *   dpar : (M + 2 D + 2) float = {dvmean[M], ds2, dlengthscale[D], dweights[D], dbias}
+ * The forward runs one workgroup per (window, 64-point block): fp64 MFMA for A, fp32 MFMA for W
+ * with L_q staged through LDS in 16-row panels, its zero tiles skipped. With `saved` (training)
+ * it keeps A as (B, M, as) floats, as = N rounded up to 64, and the clamp mask (B, as); the
+ * adjoint reads A from there, recomputes W, and from dA on runs the q / dlinv / reduce / finish
+ * kernels of gpk_variational_cov_grad_f32 on a dA it materialises in their workspace. Seven
+ * launches and two memsets on `stream`, no host synchronisation, no atomics in any sum, fixed
+ * summation orders: two calls give the same bits; a window's mean / var / dX depend on that
+ * window alone.
+ *
+ * gpk_cholesky_kl_f32: KL(q || N(0, I)) = 1/2 [|L_q|_F^2 + |m|^2 - M - sum_k log(L_q,kk^2)], one
+ * launch each way (gkl == NULL: kl (1,) out; else dm = gkl m, dchol = gkl (tril(C) - diag(1 / C_kk)),
+ * upper triangle zero), the M^2 sum in fp64 in a fixed order.
+ *
+ * Replaces (reference): upstream variational/cholesky_variational_distribution.py (forward:
+ * CholLinearOperator of the masked chol_variational_covar) inside
+ * variational/variational_strategy.py forward, and _variational_strategy.py::kl_divergence
+ * (torch.distributions.kl of the two MVNs), reached from denoising_model/DeepGP.py:28-38 when the
+ * distribution class is swapped for CholeskyVariationalDistribution; and their autograd backward.
+ *
+ * Memory per call: saved = gpk_variational_chol_saved_bytes(B, N, M, D) = (B M as + B as) * 4 bytes;
+ * the adjoint's workspace = gpk_variational_chol_adjoint_workspace_bytes(B, N, M, D): the
+ * gpk_variational_cov_grad_f32 workspace (dA and K_ZX, 2 B M as floats, and its partials) + B M as
+ * floats of W diag(gvar) + min(B, 32) M^2 doubles of dchol partials + B ceil(N / 64) (M + 66)
+ * floats of row partials. Both queries return 0 for a shape that is not served.
+ *
+ * X : (B, N, D) float   Z : (M, D) float   Linv : (M, M) double   vmean : (M,) float
+ * vchol : (M, M) float, row-major, lower read only   hyp : gpk_variational_f32's vector
+ * mean, var : (B, N) float out   flags : (1,) int or NULL   saved : NULL (inference) or device
+ * memory of the size above, 16-byte aligned   gmean, gvar : (B, N) float
+ * Forward: M <= 256, D <= 64, N >= 1, B >= 0. Adjoint: additionally N <= 256 (the shared pipeline).
+ * B = 0 launches nothing.
+ */
+size_t gpk_variational_chol_saved_bytes(int B, int N, int M, int D);
+int gpk_variational_chol_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
+                             const float* vchol, const float* hyp, int B, int N, int M, int D, float* mean,
+                             float* var, int* flags, void* saved, void* stream);
+size_t gpk_variational_chol_adjoint_workspace_bytes(int B, int N, int M, int D);
+int gpk_variational_chol_adjoint_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
+                                     const float* vchol, const float* hyp, const float* gmean,
+                                     const float* gvar, const void* saved, int B, int N, int M, int D,
+                                     void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
+                                     float* dchol, void* stream);
+int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,
+                        float* dchol, void* stream);
+
+/*
  * Batched Cholesky root of dense covariances, fused with sampling: per matrix b
  *   R R^T = cov[b] + jitter I        (lower factor, fp32, one workgroup, the matrix in LDS)
  *   samples[s, b, i] = mean[b, i] + sum_{j <= i} R[b, i, j] eps[s, b, j]   (ascending j)
