@@ -683,7 +683,37 @@ int gpk_variational_chol_f32(const float* X, const float* Z, const double* Linv,
   if (var == nullptr) return -12;
   if (saved != nullptr && ((size_t)saved & 15) != 0) return -14;
   if (B == 0) return 0;
-  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved};
+  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved, 1, 0LL};
+  return gpk_launch_var_chol(a, (hipStream_t)stream);
+}
+
+size_t gpk_variational_chol_batched_saved_bytes(int O, int B, int N, int M, int D) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_var_chol_saved_bytes(B, N, M, D);
+}
+
+int gpk_variational_chol_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                     const float* vmean, const float* vchol, const float* hyp, int O, int B,
+                                     int N, int M, int D, float* mean, float* var, int* flags, void* saved,
+                                     void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vmean == nullptr) return -5;
+  if (vchol == nullptr) return -6;
+  if (hyp == nullptr) return -7;
+  if (O < 1 || O > kGpkMaxOutputs) return -8;
+  if (B < 0) return -9;
+  if (N < 1) return -10;
+  if (M < 1 || M > 256) return -11;
+  if (D < 1 || D > 64) return -12;
+  if (mean == nullptr) return -13;
+  if (var == nullptr) return -14;
+  if (saved != nullptr && (((size_t)saved & 15) != 0 || B < 1 || gpk_var_chol_saved_bytes(B, N, M, D) == 0))
+    return -16;
+  if (B == 0) return 0;
+  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved, O,
+                   shared_x ? 0LL : (long long)B * N * D};
   return gpk_launch_var_chol(a, (hipStream_t)stream);
 }
 
@@ -718,7 +748,45 @@ int gpk_variational_chol_adjoint_f32(const float* X, const float* Z, const doubl
   if (B > 0 && gpk_var_chol_adjoint_ws_bytes(B, N, M, D) == 0) return -10;
   if (B == 0) return 0;
   GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
-                      dX, dLinv, dZ, dpar, dchol};
+                      dX, dLinv, dZ, dpar, dchol, 1, 0LL};
+  return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
+}
+
+size_t gpk_variational_chol_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_var_chol_adjoint_ws_bytes(B, N, M, D);
+}
+
+int gpk_variational_chol_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                             const float* vmean, const float* vchol, const float* hyp,
+                                             const float* gmean, const float* gvar, const void* saved, int O,
+                                             int B, int N, int M, int D, void* workspace, float* dX,
+                                             double* dLinv, float* dZ, float* dpar, float* dchol,
+                                             void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vmean == nullptr) return -5;
+  if (vchol == nullptr) return -6;
+  if (hyp == nullptr) return -7;
+  if (gmean == nullptr) return -8;
+  if (gvar == nullptr) return -9;
+  if (saved == nullptr || ((size_t)saved & 15) != 0) return -10;
+  if (O < 1 || O > kGpkMaxOutputs) return -11;
+  if (B < 0) return -12;
+  if (N < 1 || N > 256) return -13;
+  if (M < 1 || M > 256) return -14;
+  if (D < 1 || D > 64) return -15;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -16;
+  if (dX == nullptr) return -17;
+  if (dLinv == nullptr) return -18;
+  if (dZ == nullptr) return -19;
+  if (dpar == nullptr) return -20;
+  if (dchol == nullptr) return -21;
+  if (B > 0 && gpk_var_chol_adjoint_ws_bytes(B, N, M, D) == 0) return -12;
+  if (B == 0) return 0;
+  GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
+                      dX, dLinv, dZ, dpar, dchol, O, shared_x ? 0LL : (long long)B * N * D};
   return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
 }
 
@@ -730,7 +798,19 @@ int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, con
   if (gkl == nullptr && kl == nullptr) return -4;
   if (gkl != nullptr && dm == nullptr) return -6;
   if (gkl != nullptr && dchol == nullptr) return -7;
-  return gpk_launch_chol_kl(m, chol, M, kl, gkl, dm, dchol, (hipStream_t)stream);
+  return gpk_launch_chol_kl(m, chol, 1, M, kl, gkl, dm, dchol, (hipStream_t)stream);
+}
+
+int gpk_cholesky_kl_batched_f32(const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
+                                float* dm, float* dchol, void* stream) {
+  if (m == nullptr) return -1;
+  if (chol == nullptr) return -2;
+  if (O < 1 || O > kGpkMaxOutputs) return -3;
+  if (M < 1 || M > 16384) return -4;
+  if (gkl == nullptr && kl == nullptr) return -5;
+  if (gkl != nullptr && dm == nullptr) return -7;
+  if (gkl != nullptr && dchol == nullptr) return -8;
+  return gpk_launch_chol_kl(m, chol, O, M, kl, gkl, dm, dchol, (hipStream_t)stream);
 }
 
 int gpk_mvn_root_max_n(void) { return kGpkMvnRootMaxN; }

@@ -31,6 +31,10 @@
 //         out like gpk_vcg_dlinv_kernel: A (W diag gvar)^T on mfma_f64_16x16x4f64, fp64 partials.
 //   finish  every partial summed in fp64 in a fixed order; dX += gmean_i w.
 //   kl    one launch each way, the M^2 sum in a fixed order.
+// O outputs of a multi-output layer run with the output index on grid y of every launch: a
+// workgroup offsets its base pointers (X by x_stride, 0 when the inputs are shared; Z, Linv, m, C,
+// hyp, the saved state, the workspace slice and every output array by their dense leading O) and
+// is otherwise the single-output workgroup, so output o has the bits of a single-output call.
 // No atomics in any sum, fixed summation orders: two launches give the same bits; a window's
 // mean / var / dX come from that window's data alone.
 #include "gpk_common.h"
@@ -117,14 +121,21 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
   const int ncb = (N + kCB - 1) / kCB;
   const int b = blockIdx.x / ncb, cb = blockIdx.x - b * ncb;
 
-  const float* hyp = a.hyp;
-  const float* Xb = a.X + (size_t)b * N * D;
-  const float* Z = a.Z;
-  const double* Linv = a.Linv;
+  // output o: only the base pointers move, the workgroup's body is the single-output one
+  const size_t o = blockIdx.y;
+  const float* hyp = a.hyp + o * (size_t)(4 + 2 * D);
+  const float* Xb = a.X + o * (size_t)a.x_stride + (size_t)b * N * D;
+  const float* Z = a.Z + o * (size_t)M * D;
+  const double* Linv = a.Linv + o * (size_t)M * M;
+  const float* vmean = a.vmean + o * (size_t)M;
+  const float* vchol = a.vchol + o * (size_t)M * M;
+  float* saved = a.saved != nullptr ? a.saved + o * ((size_t)a.B * M * as + (size_t)a.B * as) : nullptr;
+  float* meanb = a.mean + (o * (size_t)a.B + b) * (size_t)N;
+  float* varb = a.var + (o * (size_t)a.B + b) * (size_t)N;
   const float s2 = hyp[0], jit = hyp[2], b0 = hyp[3];
 
   if (tid < 64) lsc[tid] = tid < D ? hyp[4 + D + tid] : 1.f;
-  for (int m = tid; m < MP; m += 256) vm[m] = m < M ? a.vmean[m] : 0.f;
+  for (int m = tid; m < MP; m += 256) vm[m] = m < M ? vmean[m] : 0.f;
   if (tid >= 64 && tid < 128) {   // the linear mean of this block's points
     const int j = tid - 64, col = kCB * cb + j;
     float s = 0.f;
@@ -216,7 +227,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
   //      K tiles kb <= rt, so the tiles go in descending order and a finished tile of A is never
   //      read as K again. Lane (g, c) feeds the A operand L^{-1}[16 rt + c][16 kb + 4 g + u] and
   //      the B operand K[16 kb + 4 g + u][16 w + c]; acc[r] = A[16 rt + g + 4 r][16 w + c].
-  float* Aw = a.saved != nullptr ? a.saved + (size_t)b * M * as : nullptr;
+  float* Aw = saved != nullptr ? saved + (size_t)b * M * as : nullptr;
   float* Kc = Kl + 16 * w + c;
   for (int rt = MB - 1; rt >= 0; --rt) {
     const int m = 16 * rt + c;
@@ -265,7 +276,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
 
   // ---- W = L_q^T A (the pass opens with a barrier: A is complete, zs / xs are free)
   f32x4 accW[16];
-  vch_w_pass(accW, Kl, Lp, a.vchol, M, MB, LS, tid, w, c, g);
+  vch_w_pass(accW, Kl, Lp, vchol, M, MB, LS, tid, w, c, g);
   {
     float s = 0.f;
 #pragma unroll
@@ -299,12 +310,12 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
     const bool clamp = var_i < kMinVar;
     if (col < N) {
       if (clamp) { var_i = kMinVar; clamped = 1; }   // MVN.variance clamp (fp32)
-      a.mean[(size_t)b * N + col] = sm + (lin[tid] + b0);
-      a.var[(size_t)b * N + col] = var_i;
+      meanb[col] = sm + (lin[tid] + b0);
+      varb[col] = var_i;
     }
     // the clamp passes no gradient: the adjoint masks gvar with this (padding: 0)
-    if (a.saved != nullptr)
-      a.saved[(size_t)a.B * M * as + (size_t)b * as + col] = (col < N && !clamp) ? 1.f : 0.f;
+    if (saved != nullptr)
+      saved[(size_t)a.B * M * as + (size_t)b * as + col] = (col < N && !clamp) ? 1.f : 0.f;
   }
   if (a.flags != nullptr && clamped)
     (void)__hip_atomic_fetch_or(a.flags, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -357,7 +368,14 @@ struct VchAdjArgs {
 };
 
 template <typename T>
-GPK_DEVICE T* vch_ws(const VchAdjArgs& k, size_t off) { return (T*)((char*)k.a.ws + off); }
+GPK_DEVICE T* vch_ws(const VchAdjArgs& k, size_t o, size_t off) {
+  return (T*)((char*)k.a.ws + o * k.p.total + off);
+}
+
+// Output o's slice of the forward's state: A (B, M, as), then the clamp mask (B, as).
+GPK_DEVICE const float* vch_saved(const VchAdjArgs& k, size_t o) {
+  return k.a.saved + o * ((size_t)k.a.B * k.a.M * k.p.as + (size_t)k.a.B * k.p.as);
+}
 
 // ------------------------------------------------------------------------------------------------
 // da: W, Y = L_q W, dA, the row partials
@@ -378,10 +396,16 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
   const int c = lane & 15, g = lane >> 4;
   const int ncb = k.p.ncb;
   const int b = blockIdx.x / ncb, cb = blockIdx.x - b * ncb;
-  const float* As = k.a.saved + (size_t)b * M * as;
-  const float* mask = k.a.saved + (size_t)k.a.B * M * as + (size_t)b * as;
-  float* dAb = vch_ws<float>(k, k.p.off_dA) + (size_t)b * M * as;
-  float* Wgb = vch_ws<float>(k, k.p.off_wg) + (size_t)b * M * as;
+  const size_t o = blockIdx.y;
+  const float* sv0 = vch_saved(k, o);
+  const float* As = sv0 + (size_t)b * M * as;
+  const float* mask = sv0 + (size_t)k.a.B * M * as + (size_t)b * as;
+  const float* gmean = k.a.gmean + (o * (size_t)k.a.B + b) * (size_t)N;
+  const float* gvar = k.a.gvar + (o * (size_t)k.a.B + b) * (size_t)N;
+  const float* vmean = k.a.vmean + o * (size_t)M;
+  const float* vchol = k.a.vchol + o * (size_t)M * M;
+  float* dAb = vch_ws<float>(k, o, k.p.off_dA) + (size_t)b * M * as;
+  float* Wgb = vch_ws<float>(k, o, k.p.off_wg) + (size_t)b * M * as;
 
   for (int e = tid; e < MP * kCB; e += 256) {
     const int m = e >> 6, j = e & 63;
@@ -391,16 +415,16 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
   if (tid < 64) {
     const int col = kCB * cb + tid;
     const bool ok = col < N;
-    const float gmv = k.a.gmean[ok ? (size_t)b * N + col : 0];
-    const float gvv = k.a.gvar[ok ? (size_t)b * N + col : 0];
+    const float gmv = gmean[ok ? col : 0];
+    const float gvv = gvar[ok ? col : 0];
     gm[tid] = ok ? gmv : 0.f;
     gv[tid] = (ok && mask[col] != 0.f) ? gvv : 0.f;
   }
-  for (int m = tid; m < MP; m += 256) vm[m] = m < M ? k.a.vmean[m] : 0.f;
+  for (int m = tid; m < MP; m += 256) vm[m] = m < M ? vmean[m] : 0.f;
 
   // ---- W = L_q^T A (the pass opens with a barrier), kept in LDS; W diag(gvar) -> workspace
   f32x4 accW[16];
-  vch_w_pass(accW, Al, Lp, k.a.vchol, M, MB, LS, tid, w, c, g);
+  vch_w_pass(accW, Al, Lp, vchol, M, MB, LS, tid, w, c, g);
   {
     const int col = 16 * w + c;
     const float gvc = gv[col];
@@ -420,7 +444,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
   //      A operand L_q[16 mt + c][16 kb + 4 g + u] and the B operand W[16 kb + 4 g + u][16 w + c].
   for (int mt = 0; mt < MB; ++mt) {
     lds_barrier();   // the previous panel's reads are done (first pass: W is written)
-    vch_stage_panel(k.a.vchol, M, mt, Lp, LS, tid);
+    vch_stage_panel(vchol, M, mt, Lp, LS, tid);
     lds_barrier();
     f32x4 y = {0.f, 0.f, 0.f, 0.f};
     for (int kb = 0; kb <= mt; ++kb) {
@@ -445,22 +469,22 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
   if (tid < M) {
     float s = 0.f;
     for (int j = 0; j < kCB; ++j) s = __builtin_fmaf(gm[j], Al[(size_t)tid * kKS + j], s);
-    vch_ws<float>(k, k.p.off_dm)[wg * M + tid] = s;
+    vch_ws<float>(k, o, k.p.off_dm)[wg * M + tid] = s;
   }
   if (tid < 64) {
     float s = 0.f;
     if (tid < D) {
-      const float* Xb = k.a.X + (size_t)b * N * D;
+      const float* Xb = k.a.X + o * (size_t)k.a.x_stride + (size_t)b * N * D;
       const int nv = N - kCB * cb < kCB ? N - kCB * cb : kCB;
       for (int j = 0; j < nv; ++j) s = __builtin_fmaf(gm[j], Xb[(size_t)(kCB * cb + j) * D + tid], s);
     }
-    vch_ws<float>(k, k.p.off_xg)[wg * 64 + tid] = s;
+    vch_ws<float>(k, o, k.p.off_xg)[wg * 64 + tid] = s;
   }
   if (w == 1) {
     const float sv = wave_sum(gv[lane]), sg = wave_sum(gm[lane]);
     if (lane == 0) {
-      vch_ws<float>(k, k.p.off_sc)[wg * 2] = sv;
-      vch_ws<float>(k, k.p.off_sc)[wg * 2 + 1] = sg;
+      vch_ws<float>(k, o, k.p.off_sc)[wg * 2] = sv;
+      vch_ws<float>(k, o, k.p.off_sc)[wg * 2 + 1] = sg;
     }
   }
 }
@@ -486,9 +510,10 @@ __global__ __launch_bounds__(256) void gpk_vchol_gram_kernel(VchAdjArgs k) {
   const int bj = pr;   // bj <= bi
   const int b0 = sp * k.p.WS;
   const int b1 = b0 + k.p.WS < B ? b0 + k.p.WS : B;
-  const float* Aw = k.a.saved;
-  const float* Wg = vch_ws<float>(k, k.p.off_wg);
-  double* Cp = vch_ws<double>(k, k.p.off_cp) + (size_t)sp * M * M;
+  const size_t o = blockIdx.y;
+  const float* Aw = vch_saved(k, o);
+  const float* Wg = vch_ws<float>(k, o, k.p.off_wg);
+  double* Cp = vch_ws<double>(k, o, k.p.off_cp) + (size_t)sp * M * M;
 
   f64x4 acc[4];
 #pragma unroll
@@ -539,6 +564,8 @@ __global__ __launch_bounds__(256) void gpk_vchol_finish_kernel(VchAdjArgs k, int
   const int N = k.a.N, M = k.a.M, D = k.a.D, B = k.a.B;
   const int tid = threadIdx.x;
   const int blk = blockIdx.x;
+  const size_t o = blockIdx.y;
+  float* dpar = k.a.dpar + o * (size_t)(M + 2 * D + 2);
   const long long nwg = (long long)B * k.p.ncb;
   if (blk < nC) {
     const long long e = (long long)blk * 256 + tid, mm = (long long)M * M;
@@ -546,30 +573,30 @@ __global__ __launch_bounds__(256) void gpk_vchol_finish_kernel(VchAdjArgs k, int
     const int m = (int)(e / M), kc = (int)(e - (long long)m * M);
     double s = 0.0;
     if (kc <= m) {
-      const double* Cp = vch_ws<double>(k, k.p.off_cp);
+      const double* Cp = vch_ws<double>(k, o, k.p.off_cp);
       for (int sp = 0; sp < k.p.nsplit; ++sp) s += Cp[(size_t)sp * mm + e];
     }
-    k.a.dchol[e] = (float)(2.0 * s);
+    k.a.dchol[o * (size_t)mm + e] = (float)(2.0 * s);
     return;
   }
   if (blk < nC + nV) {
     const int e = (blk - nC) * 256 + tid;
     if (e < M) {
-      const float* dmp = vch_ws<float>(k, k.p.off_dm);
+      const float* dmp = vch_ws<float>(k, o, k.p.off_dm);
       double s = 0.0;
       for (long long wg = 0; wg < nwg; ++wg) s += dmp[wg * M + e];
-      k.a.dpar[e] = (float)s;
+      dpar[e] = (float)s;
     } else if (e < M + D) {
       const int d = e - M;
-      const float* xg = vch_ws<float>(k, k.p.off_xg);
+      const float* xg = vch_ws<float>(k, o, k.p.off_xg);
       double s = 0.0;
       for (long long wg = 0; wg < nwg; ++wg) s += xg[wg * 64 + d];
-      k.a.dpar[M + 1 + D + d] = (float)s;
+      dpar[M + 1 + D + d] = (float)s;
     }
     return;
   }
   if (blk == nC + nV) {
-    const float* sc = vch_ws<float>(k, k.p.off_sc);
+    const float* sc = vch_ws<float>(k, o, k.p.off_sc);
     double sv = 0.0, sg = 0.0;
     for (long long wg = tid; wg < nwg; wg += 256) {
       sv += sc[2 * wg];
@@ -586,8 +613,8 @@ __global__ __launch_bounds__(256) void gpk_vchol_finish_kernel(VchAdjArgs k, int
       __syncthreads();
     }
     if (tid == 0) {
-      k.a.dpar[M] = (float)((double)k.a.dpar[M] + sh[0][0]);
-      k.a.dpar[M + 1 + 2 * D] = (float)sh[1][0];
+      dpar[M] = (float)((double)dpar[M] + sh[0][0]);
+      dpar[M + 1 + 2 * D] = (float)sh[1][0];
     }
     return;
   }
@@ -595,7 +622,8 @@ __global__ __launch_bounds__(256) void gpk_vchol_finish_kernel(VchAdjArgs k, int
   if (e >= (long long)B * N * D) return;
   const long long pt = e / D;
   const int d = (int)(e - pt * D);
-  k.a.dX[e] = __builtin_fmaf(k.a.gmean[pt], k.a.hyp[4 + d], k.a.dX[e]);
+  const size_t eo = o * (size_t)B * N * D + e;
+  k.a.dX[eo] = __builtin_fmaf(k.a.gmean[o * (size_t)B * N + pt], k.a.hyp[o * (size_t)(4 + 2 * D) + 4 + d], k.a.dX[eo]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -606,6 +634,9 @@ __global__ __launch_bounds__(256) void gpk_chol_kl_fwd_kernel(const float* __res
                                                               float* __restrict__ kl) {
   __shared__ double sh[256];
   const int tid = threadIdx.x;
+  const size_t o = blockIdx.y;
+  m += o * (size_t)M;
+  C += o * (size_t)M * M;
   double s = 0.0;
   for (int e = tid; e < M * M; e += 256) {
     const int r = e / M, kc = e - r * M;
@@ -621,7 +652,7 @@ __global__ __launch_bounds__(256) void gpk_chol_kl_fwd_kernel(const float* __res
     if (tid < off) sh[tid] += sh[tid + off];
     __syncthreads();
   }
-  if (tid == 0) kl[0] = (float)(0.5 * (sh[0] - (double)M));
+  if (tid == 0) kl[o] = (float)(0.5 * (sh[0] - (double)M));
 }
 
 __global__ __launch_bounds__(256) void gpk_chol_kl_bwd_kernel(const float* __restrict__ m,
@@ -629,7 +660,12 @@ __global__ __launch_bounds__(256) void gpk_chol_kl_bwd_kernel(const float* __res
                                                               const float* __restrict__ gkl,
                                                               float* __restrict__ dm, float* __restrict__ dC) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  const float g = gkl[0];
+  const size_t o = blockIdx.y;
+  const float g = gkl[o];
+  m += o * (size_t)M;
+  C += o * (size_t)M * M;
+  dm += o * (size_t)M;
+  dC += o * (size_t)M * M;
   if (e < M * M) {
     const int r = e / M, kc = e - r * M;
     const float v = C[e];
@@ -670,7 +706,7 @@ size_t gpk_var_chol_adjoint_ws_bytes(int B, int N, int M, int D) {
 }
 
 int gpk_launch_var_chol(const GpkVarCholArgs& a, hipStream_t stream) {
-  if (!vch_fwd_shape_ok(a.B, a.N, a.M, a.D)) return -7;
+  if (!vch_fwd_shape_ok(a.B, a.N, a.M, a.D) || a.O < 1 || a.O > 65535) return -7;
   vch_set_lds_once();
   const size_t lds = vch_fwd_lds(a.M, a.D);
   if (lds > 160 * 1024) return -9;
@@ -680,44 +716,48 @@ int gpk_launch_var_chol(const GpkVarCholArgs& a, hipStream_t stream) {
     const hipError_t e = hipMemsetAsync(a.flags, 0, sizeof(int), stream);
     if (e != hipSuccess) return (int)e;
   }
-  hipLaunchKernelGGL(gpk_vchol_fwd_kernel, dim3((unsigned)(a.B * ncb)), dim3(256), lds, stream, a, as);
+  hipLaunchKernelGGL(gpk_vchol_fwd_kernel, dim3((unsigned)(a.B * ncb), (unsigned)a.O), dim3(256), lds, stream, a, as);
   return (int)hipGetLastError();
 }
 
 int gpk_launch_var_chol_adjoint(const GpkVarCholAdjArgs& a, hipStream_t stream) {
-  if (gpk_var_chol_adjoint_ws_bytes(a.B, a.N, a.M, a.D) == 0) return -10;
+  if (gpk_var_chol_adjoint_ws_bytes(a.B, a.N, a.M, a.D) == 0 || a.O < 1 || a.O > 65535) return -10;
   vch_set_lds_once();
+  const unsigned O = (unsigned)a.O;
   VchAdjArgs k{a, vch_plan(a.B, a.N, a.M, a.D)};
   const size_t lds = vch_da_lds(k.p.MP);
   if (lds > 160 * 1024) return -12;
-  hipLaunchKernelGGL(gpk_vchol_da_kernel, dim3((unsigned)(a.B * k.p.ncb)), dim3(256), lds, stream, k);
-  hipLaunchKernelGGL(gpk_vchol_gram_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit)), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vchol_da_kernel, dim3((unsigned)(a.B * k.p.ncb), O), dim3(256), lds, stream, k);
+  hipLaunchKernelGGL(gpk_vchol_gram_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit), O), dim3(256), 0, stream, k);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  // from dA on: the shared pipeline (its dpar slice {0[M], ds2, dl[D]} is the head of ours)
+  // from dA on: the shared pipeline on our slices (its plan is the head of each) and our dpar
+  // rows (its {0[M], ds2, dl[D]} is the head of each)
   GpkVarCovGradArgs t{};
   t.X = a.X; t.Z = a.Z; t.Linv = a.Linv; t.vstd = a.vmean; t.hyp = a.hyp;
   t.state = nullptr; t.gcov = nullptr;
-  t.B = a.B; t.N = a.N; t.M = a.M; t.D = a.D; t.O = 1;
-  t.x_stride = 0;
+  t.B = a.B; t.N = a.N; t.M = a.M; t.D = a.D; t.O = a.O;
+  t.x_stride = a.x_stride;
   t.ws = a.ws; t.dX = a.dX; t.dLinv = a.dLinv; t.dZ = a.dZ; t.dpar = a.dpar;
-  const int rc = gpk_launch_var_cov_grad_from_dA(t, stream);
+  const int rc = gpk_launch_var_cov_grad_from_dA(t, k.p.total, a.M + 2 * a.D + 2, stream);
   if (rc != 0) return rc;
   const int nC = (int)(((long long)a.M * a.M + 255) / 256);
   const int nV = (a.M + a.D + 255) / 256;
   const long long nX = ((long long)a.B * a.N * a.D + 255) / 256;
   if (nC + nV + 1 + nX > 0x7fffffffLL) return -10;
-  hipLaunchKernelGGL(gpk_vchol_finish_kernel, dim3((unsigned)(nC + nV + 1 + nX)), dim3(256), 0, stream, k, nC, nV);
+  hipLaunchKernelGGL(gpk_vchol_finish_kernel, dim3((unsigned)(nC + nV + 1 + nX), O), dim3(256), 0, stream, k, nC, nV);
   return (int)hipGetLastError();
 }
 
-int gpk_launch_chol_kl(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,
-                       float* dchol, hipStream_t stream) {
+int gpk_launch_chol_kl(const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
+                       float* dm, float* dchol, hipStream_t stream) {
+  if (O < 1 || O > 65535) return -3;
   if (gkl == nullptr) {
-    hipLaunchKernelGGL(gpk_chol_kl_fwd_kernel, dim3(1), dim3(256), 0, stream, m, chol, M, kl);
+    hipLaunchKernelGGL(gpk_chol_kl_fwd_kernel, dim3(1, (unsigned)O), dim3(256), 0, stream, m, chol, M, kl);
   } else {
     const int nb = (M * M + M + 255) / 256;
-    hipLaunchKernelGGL(gpk_chol_kl_bwd_kernel, dim3(nb), dim3(256), 0, stream, m, chol, M, gkl, dm, dchol);
+    hipLaunchKernelGGL(gpk_chol_kl_bwd_kernel, dim3(nb, (unsigned)O), dim3(256), 0, stream, m, chol, M, gkl, dm,
+                       dchol);
   }
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;

@@ -31,5 +31,10 @@ int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream);
 // Same kernels, same workspace plan (the query returns the plan's size, 0 for a refused shape);
 // state and gcov are not read, the dw and kxx partials are zero-filled so that dpar[0..M) comes
 // out 0 and ds2 / dlengthscale carry the K_ZX part alone; vstd only needs to be readable.
+// O >= 1 outputs on grid y, as gpk_launch_var_cov_grad. The caller's workspace slices and dpar
+// rows may be longer than the plan's: output o's slice starts ws_stride bytes (a multiple of
+// 16, >= the plan's size) after output o - 1's, its dpar row dpar_stride floats (>= M + 1 + D)
+// after; the pipeline writes the head of each.
 size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, int* as);
-int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, hipStream_t stream);
+int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
+                                    hipStream_t stream);

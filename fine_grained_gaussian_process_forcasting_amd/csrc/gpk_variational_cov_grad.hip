@@ -90,11 +90,13 @@ struct VcgArgs {
   GpkVarCovGradArgs a;
   VcgPlan p;
   long long state_stride;   // floats between two outputs' forward workspaces
+  size_t ws_stride;         // bytes between two outputs' workspace slices (>= p.total)
+  int dpar_stride;          // floats between two outputs' dpar rows (>= M + 1 + D)
 };
 
 template <typename T>
 GPK_DEVICE T* vcg_ws(const VcgArgs& k, size_t o, size_t off) {
-  return (T*)((char*)k.a.ws + o * k.p.total + off);
+  return (T*)((char*)k.a.ws + o * k.ws_stride + off);
 }
 
 // Column means of Z / l in the forward's order: 8 partial sums per column over rows m = k mod 8,
@@ -722,7 +724,7 @@ __global__ __launch_bounds__(256) void gpk_vcg_reduce_kernel(VcgArgs k) {
     const float* dwp = vcg_ws<float>(k, o, k.p.off_dw);
     double s = 0.0;
     for (int b = 0; b < B; ++b) s += dwp[(size_t)b * M + m];
-    k.a.dpar[o * (size_t)(M + 1 + D) + m] = (float)(2.0 * (double)k.a.vstd[o * (size_t)M + m] * s);
+    k.a.dpar[o * (size_t)k.dpar_stride + m] = (float)(2.0 * (double)k.a.vstd[o * (size_t)M + m] * s);
   }
 }
 
@@ -737,7 +739,7 @@ __global__ __launch_bounds__(256) void gpk_vcg_finish_kernel(VcgArgs k) {
   const double* qt = vcg_ws<double>(k, o, k.p.off_qt);
   const float* xvp = vcg_ws<float>(k, o, k.p.off_xv);
   const float* cp = vcg_ws<float>(k, o, k.p.off_cp);
-  float* dpar = k.a.dpar + o * (size_t)(M + 1 + D);
+  float* dpar = k.a.dpar + o * (size_t)k.dpar_stride;
 
   // dl_d: four interleaved partial sums per dimension, then q ascending
   {
@@ -799,31 +801,42 @@ size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, in
   return p.total;
 }
 
-int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, hipStream_t stream) {
+int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
+                                    hipStream_t stream) {
   vcg_set_lds_once();
-  if (!vcg_shape_ok(a.B, a.N, a.M, a.D) || a.O != 1) return -9;
-  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0};
+  if (!vcg_shape_ok(a.B, a.N, a.M, a.D) || a.O < 1 || a.O > 65535) return -9;
+  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0, ws_stride, dpar_stride};
+  if (ws_stride < k.p.total || (ws_stride & 15) != 0 || dpar_stride < a.M + 1 + a.D) return -9;
+  const unsigned O = (unsigned)a.O;
   const unsigned gq = (unsigned)(k.p.nchunk * k.p.ncb);
   const size_t lds = vcg_q_lds(k.p.MP, k.p.Dq);
   const long long nred = ((long long)a.M * a.M + (long long)k.p.MP * k.p.Dq + 255) / 256;
-  // what t and kxx would have written: no dw, no K_XX partials
-  hipError_t e = hipMemsetAsync((char*)a.ws + k.p.off_dw, 0, (size_t)a.B * a.M * sizeof(float), stream);
-  if (e == hipSuccess)
-    e = hipMemsetAsync((char*)a.ws + k.p.off_cp, 0, (size_t)gq * 128 * sizeof(float), stream);
+  // what t and kxx would have written: no dw, no K_XX partials. One strided fill each for all
+  // the outputs' slices (the slice stride is the pitch), so the launch count does not grow with O.
+  const size_t ndw = (size_t)a.B * a.M * sizeof(float), ncp = (size_t)gq * 128 * sizeof(float);
+  hipError_t e;
+  if (O == 1) {
+    e = hipMemsetAsync((char*)a.ws + k.p.off_dw, 0, ndw, stream);
+    if (e == hipSuccess) e = hipMemsetAsync((char*)a.ws + k.p.off_cp, 0, ncp, stream);
+  } else {
+    e = hipMemset2DAsync((char*)a.ws + k.p.off_dw, ws_stride, 0, ndw, O, stream);
+    if (e == hipSuccess) e = hipMemset2DAsync((char*)a.ws + k.p.off_cp, ws_stride, 0, ncp, O, stream);
+  }
   if (e != hipSuccess) return (int)e;
-  if (k.p.Dq == 16) hipLaunchKernelGGL(gpk_vcg_q_kernel<1>, dim3(gq, 1), dim3(256), lds, stream, k);
-  else if (k.p.Dq == 32) hipLaunchKernelGGL(gpk_vcg_q_kernel<2>, dim3(gq, 1), dim3(256), lds, stream, k);
-  else hipLaunchKernelGGL(gpk_vcg_q_kernel<4>, dim3(gq, 1), dim3(256), lds, stream, k);
-  hipLaunchKernelGGL(gpk_vcg_dlinv_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit), 1), dim3(256), 0, stream, k);
-  hipLaunchKernelGGL(gpk_vcg_reduce_kernel, dim3((unsigned)nred, 1), dim3(256), 0, stream, k);
-  hipLaunchKernelGGL(gpk_vcg_finish_kernel, dim3(1, 1), dim3(256), 0, stream, k);
+  if (k.p.Dq == 16) hipLaunchKernelGGL(gpk_vcg_q_kernel<1>, dim3(gq, O), dim3(256), lds, stream, k);
+  else if (k.p.Dq == 32) hipLaunchKernelGGL(gpk_vcg_q_kernel<2>, dim3(gq, O), dim3(256), lds, stream, k);
+  else hipLaunchKernelGGL(gpk_vcg_q_kernel<4>, dim3(gq, O), dim3(256), lds, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_dlinv_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit), O), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_reduce_kernel, dim3((unsigned)nred, O), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_finish_kernel, dim3(1, O), dim3(256), 0, stream, k);
   return (int)hipGetLastError();
 }
 
 int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream) {
   vcg_set_lds_once();
   if (!vcg_shape_ok(a.B, a.N, a.M, a.D)) return -9;
-  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0};
+  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), 0, 0, a.M + 1 + a.D};
+  k.ws_stride = k.p.total;
   k.state_stride = (long long)a.B * a.M * k.p.as + (long long)a.B * 64;
   const unsigned O = (unsigned)a.O;
   const int nrb = (a.M + 63) / 64;

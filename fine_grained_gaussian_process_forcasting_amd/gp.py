@@ -675,12 +675,15 @@ class CholeskyVariationalDistribution(nn.Module):
 
     def kl_divergence(self) -> torch.Tensor:
         """KL(q || N(0, I)) = 1/2 (|L_q|_F^2 + |m|^2 - M - sum_k log L_q,kk^2): one gfx950 launch
-        each way (gpk::cholesky_kl) for the unbatched CUDA fp32 layer, the closed form in torch
-        elsewhere."""
+        each way for a CUDA fp32 layer (gpk::cholesky_kl for one output, gpk::cholesky_kl_batched
+        for the (O, M) mean of a multi-output layer -> (O,)), the closed form in torch elsewhere."""
         m = self.variational_mean
         C = self.chol_variational_covar
-        if m.is_cuda and m.dim() == 1 and m.dtype == torch.float32 and C.dtype == torch.float32:
-            return torch.ops.gpk.cholesky_kl(m, C).reshape(())
+        if m.is_cuda and m.dtype == torch.float32 and C.dtype == torch.float32:
+            if m.dim() == 1:
+                return torch.ops.gpk.cholesky_kl(m, C).reshape(())
+            if m.dim() == 2 and 1 <= m.shape[0] <= 65535 and m.shape[1] <= 16384:
+                return torch.ops.gpk.cholesky_kl_batched(m, C)
         return cholesky_kl_closed_form(m, C)
 
 
@@ -865,14 +868,19 @@ class VariationalStrategy(nn.Module):
         return mean, var, flag, cov
 
     def _call_chol(self, x: torch.Tensor) -> MultivariateNormal:
-        """q(f) with a CholeskyVariationalDistribution. One output, CUDA fp32 inputs and a shape the
-        kernels' queries accept (M <= 256, D <= 64; N <= 256 when a gradient can flow):
-        ops_autograd.variational_predict_chol (gpk_variational_chol_f32 and its HIP adjoint). Every
-        other case -- a refused shape, another dtype, a multi-output layer (inducing points
-        (O, M, D), one torch evaluation per output) -- is variational_chol_predict in torch from the
-        same shared K_ZZ factor (KzzCache); the dense covariance behind covariance_matrix / rsample
-        is torch in every case."""
-        from .ops_autograd import _mean_params, _mean_params_batched, variational_predict_chol
+        """q(f) with a CholeskyVariationalDistribution. CUDA fp32 inputs and a shape the kernels'
+        queries accept (M <= 256, D <= 64; N <= 256 when a gradient can flow): one output runs
+        ops_autograd.variational_predict_chol (gpk_variational_chol_f32 and its HIP adjoint), a
+        multi-output layer (inducing points (O, M, D), x (..., O, N, D)) runs its O outputs on ONE
+        launch chain each way (ops_autograd.variational_predict_chol_batched,
+        gpk_variational_chol_batched_f32): the O K_ZZ factors are one cache entry, DeepGPLayer's
+        stride-0 expansion of the inputs is read in place (no (O, B, N, D) copy) and the per-output
+        dLinv flow into one batched K_ZZ adjoint. Every other case -- a refused shape, another
+        dtype, CPU tensors -- is variational_chol_predict in torch from the same shared K_ZZ factor
+        (KzzCache), one evaluation per output for a multi-output layer; the dense covariance behind
+        covariance_matrix / rsample is torch in every case."""
+        from .ops_autograd import (_mean_params, _mean_params_batched, variational_predict_chol,
+                                   variational_predict_chol_batched)
         model = self.model
         kern = model.covar_module
         q = self._variational_distribution
@@ -887,23 +895,40 @@ class VariationalStrategy(nn.Module):
             batch = x.shape[:-3]
             s2 = kern.outputscale.reshape(O)
             ls = kern.base_kernel.lengthscale.reshape(O, -1)
-            Linv = self._kzz_cache.factor(Z, s2, ls, jitter, key)
-            w, b0 = _mean_params_batched(model.mean_module, O, D, x.device)
-            xo = x.movedim(-3, 0).reshape(O, -1, N, D)
             vm, vc = q.variational_mean.reshape(O, M), q.chol_variational_covar.reshape(O, M, M)
-            outs = [variational_chol_predict(xo[o], Z[o], Linv[o], vm[o], vc[o], s2[o], ls[o],
-                                             w[o] if w.dim() == 2 else w, b0[o] if b0.numel() == O else b0[0],
-                                             jitter) for o in range(O)]
-            mean = torch.stack([m for m, _ in outs]).reshape(O, *batch, N).movedim(0, -2)
-            var = torch.stack([v for _, v in outs]).reshape(O, *batch, N).movedim(0, -2)
-            self._kzz_cache.note_consumers(mean, var)
-            self._kzz_cache.check_pending()
+            nwin = x.numel() // (O * N * D) if x.numel() > 0 else 0
+            flag = None
+            on_kernels = (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32
+                          and vc.dtype == torch.float32
+                          and ops.variational_chol_batched_supported(O, nwin, N, M, D,
+                                                                     adjoint=torch.is_grad_enabled()))
+            xo = x.movedim(-3, 0).reshape(O, -1, N, D)     # a view of an expanded x: no copy until read
+            if on_kernels:
+                if x.stride(-3) == 0 or O == 1:     # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
+                    xk = x[..., 0, :, :].reshape(-1, N, D)
+                else:
+                    xk = xo
+                mean, var, flag, Linv = variational_predict_chol_batched(
+                    xk, Z, vm, vc, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
+                    return_linv=True)
+                mean = mean.reshape(O, *batch, N).movedim(0, -2)
+                var = var.reshape(O, *batch, N).movedim(0, -2)
+            else:
+                Linv = self._kzz_cache.factor(Z, s2, ls, jitter, key)
+                w, b0 = _mean_params_batched(model.mean_module, O, D, x.device)
+                outs = [variational_chol_predict(xo[o], Z[o], Linv[o], vm[o], vc[o], s2[o], ls[o],
+                                                 w[o] if w.dim() == 2 else w, b0[o] if b0.numel() == O else b0[0],
+                                                 jitter) for o in range(O)]
+                mean = torch.stack([m for m, _ in outs]).reshape(O, *batch, N).movedim(0, -2)
+                var = torch.stack([v for _, v in outs]).reshape(O, *batch, N).movedim(0, -2)
+                self._kzz_cache.note_consumers(mean, var)
+                self._kzz_cache.check_pending()
 
             def cov():
                 return torch.stack([variational_chol_dense_covariance(xo[o], Z[o], Linv[o], vc[o], s2[o], ls[o],
                                                                       jitter).reshape(*batch, N, N)
                                     for o in range(O)], dim=-3)
-            return MultivariateNormal(mean.contiguous(), var.contiguous(), covar_fn=cov)
+            return MultivariateNormal(mean.contiguous(), var.contiguous(), clamp_flag=flag, covar_fn=cov)
 
         batch = x.shape[:-2]
         M = Z.shape[0]

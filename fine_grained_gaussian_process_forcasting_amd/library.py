@@ -25,6 +25,9 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::variational_chol_adj(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved)
       -> (dX, dLinv, dZ, dpar, dchol)
   gpk::cholesky_kl(m, chol) -> kl (1,)                                        [autograd]
+  gpk::variational_chol_fwd_batched / gpk::variational_chol_adj_batched / gpk::cholesky_kl_batched /
+  gpk::cholesky_kl_grad_batched
+      the three above for the O outputs of a multi-output layer, one launch chain each way [autograd]
   gpk::gauss_ell(y, mean, var, noise) -> ell (R,)                             [autograd]
   gpk::meanfield_kl(m, s) -> kl (1,)                                          [autograd]
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
@@ -921,3 +924,126 @@ def _ckl_backward(ctx, gkl):
 
 
 cholesky_kl.register_autograd(_ckl_backward, setup_context=_ckl_setup)
+
+# ---------------------------------------------------------------------------
+# Cholesky q(u) of a multi-output layer: gpk_variational_chol_batched_f32 /
+# gpk_variational_chol_adjoint_batched_f32 / gpk_cholesky_kl_batched_f32 (O outputs, every launch once)
+# ---------------------------------------------------------------------------
+
+
+def _chol_saved_numel_batched(x, Z, save):
+    B, N, D = x.shape[-3:]
+    if not save or B < 1:
+        return 0
+    O, M, _ = Z.shape
+    return _native.lib().gpk_variational_chol_batched_saved_bytes(O, B, N, M, D) // 4
+
+
+@torch.library.custom_op("gpk::variational_chol_fwd_batched", mutates_args=(), device_types="cuda")
+def variational_chol_fwd_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor, s2: Tensor,
+                                 ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
+                                 save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """gpk::variational_chol_fwd for O outputs: x (B, N, D) shared by the outputs, or (O, B, N, D);
+    Linv (O, M, M), Z (O, M, D), vmean (O, M), vchol (O, M, M), s2 (O,), ls (O, D) or (O, 1); the
+    mean per output (w (O, D), b0 (O,)) or shared (w (D,), b0 one value) -> (mean, var (O, B, N),
+    clamp flags (1,), packed hyper (O, 4 + 2D), saved state)."""
+    hyper = _var_hyper_batched(x, Z.shape[0], s2, ls, w, b0, jitter)
+    out = ops.variational_chol_forward_batched(x, Z, Linv, vmean, vchol, hyper, save=save)
+    saved = out.saved if out.saved is not None else x.new_empty(0)
+    return out.mean, out.var, out.flags, hyper, saved
+
+
+@variational_chol_fwd_batched.register_fake
+def _(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save=False):
+    B, N, D = x.shape[-3:]
+    O = Z.shape[0]
+    return (x.new_empty(O, B, N), x.new_empty(O, B, N), x.new_empty(1, dtype=torch.int32),
+            x.new_empty(O, 4 + 2 * D), x.new_empty(_chol_saved_numel_batched(x, Z, save)))
+
+
+@torch.library.custom_op("gpk::variational_chol_adj_batched", mutates_args=(), device_types="cuda")
+def variational_chol_adj_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor,
+                                 hyper: Tensor, gmean: Tensor, gvar: Tensor,
+                                 saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX (O, B, N, D) per output, dLinv (O, M, M), dZ (O, M, D), dpar (O, M + 2D + 2) =
+    [dvmean (M), ds2, dls (D), dw (D), db0] per output, dchol (O, M, M) lower)."""
+    return ops.variational_chol_adjoint_batched(x, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+
+
+@variational_chol_adj_batched.register_fake
+def _(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved):
+    O, M, D = Z.shape
+    B, N = x.shape[-3], x.shape[-2]
+    return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(O, M + 2 * D + 2), x.new_empty(O, M, M))
+
+
+def _vcholb_setup(ctx, inputs, output):
+    x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter = inputs[:10]
+    ctx.save_for_backward(x, Linv, Z, vmean, vchol, s2, ls, w, b0, output[3], output[4])
+    ctx.mark_non_differentiable(output[2], output[3], output[4])
+
+
+def _vcholb_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
+    x, Linv, Z, vmean, vchol, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
+    O, M, D = Z.shape
+    B, N = x.shape[-3], x.shape[-2]
+    if saved.numel() == 0 and B > 0:
+        raise RuntimeError("gpk::variational_chol_fwd_batched was called with save=False; no backward")
+    if gmean is None:
+        gmean = x.new_zeros(O, B, N)
+    if gvar is None:
+        gvar = x.new_zeros(O, B, N)
+    if B == 0:
+        dX, dLinv, dZ = x.new_zeros(O, B, N, D), torch.zeros_like(Linv), torch.zeros_like(Z)
+        dpar, dchol = x.new_zeros(O, M + 2 * D + 2), x.new_zeros(O, M, M)
+    else:
+        dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_adj_batched(
+            x, Linv, Z, vmean, vchol, hyper, gmean.contiguous(), gvar.contiguous(), saved)
+    if x.dim() == 3:
+        dX = dX.sum(0)                      # inputs shared by the outputs
+    dls = dpar[:, M + 1:M + 1 + D]
+    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
+    dw = dpar[:, M + 1 + D:M + 1 + 2 * D]
+    dw = dw.sum(0).reshape(w.shape) if w.numel() == D else dw.reshape(w.shape)   # a mean shared by the outputs
+    db0 = dpar[:, M + 1 + 2 * D]
+    db0 = db0.sum().reshape(b0.shape) if b0.numel() == 1 else db0.reshape(b0.shape)
+    return (dX, dLinv, dZ, dpar[:, :M].reshape(vmean.shape), dchol.reshape(vchol.shape),
+            dpar[:, M].reshape(s2.shape), dls, dw, db0, None, None)
+
+
+variational_chol_fwd_batched.register_autograd(_vcholb_backward, setup_context=_vcholb_setup)
+
+
+@torch.library.custom_op("gpk::cholesky_kl_batched", mutates_args=(), device_types="cuda")
+def cholesky_kl_batched(m: Tensor, chol: Tensor) -> Tensor:
+    """(O,) KL(N(m_o, L_o L_o^T) || N(0, I)), L_o = tril(chol_o): m (O, M), chol (O, M, M)."""
+    return ops.cholesky_kl_batched(m, chol)
+
+
+@cholesky_kl_batched.register_fake
+def _(m, chol):
+    return m.new_empty(m.shape[0])
+
+
+@torch.library.custom_op("gpk::cholesky_kl_grad_batched", mutates_args=(), device_types="cuda")
+def cholesky_kl_grad_batched(m: Tensor, chol: Tensor, gkl: Tensor) -> Tuple[Tensor, Tensor]:
+    return ops.cholesky_kl_grad_batched(m, chol, gkl)
+
+
+@cholesky_kl_grad_batched.register_fake
+def _(m, chol, gkl):
+    return torch.empty_like(m), torch.empty_like(chol)
+
+
+def _cklb_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _cklb_backward(ctx, gkl):
+    m, chol = ctx.saved_tensors
+    dm, dchol = torch.ops.gpk.cholesky_kl_grad_batched(m, chol, gkl.contiguous())
+    return dm, dchol
+
+
+cholesky_kl_batched.register_autograd(_cklb_backward, setup_context=_cklb_setup)

@@ -1422,3 +1422,135 @@ def cholesky_kl_grad(m, chol, gkl):
                                            dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
     _native.check(rc, "gpk_cholesky_kl_f32")
     return dm, dchol
+
+
+# ---------------------------------------------------------------------------
+# Cholesky q(u) for O outputs at once: gpk_variational_chol_batched_f32 / _adjoint_batched_f32,
+# gpk_cholesky_kl_batched_f32 (the output index on grid y of every launch)
+# ---------------------------------------------------------------------------
+def variational_chol_batched_supported(O: int, B: int, N: int, M: int, D: int, adjoint: bool = False) -> bool:
+    """Whether the batched Cholesky-q(u) kernels serve the shape (the two batched *_bytes
+    queries: 1 <= O <= 65535 and the single-output bounds)."""
+    if B < 1:
+        return False
+    lib = _native.lib()
+    if adjoint:
+        return lib.gpk_variational_chol_adjoint_batched_workspace_bytes(O, B, N, M, D) > 0
+    return lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D) > 0
+
+
+def _chol_batched_args(X, Z, Linv, vmean, vchol, hyper):
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+    O, M, D = Z.shape
+    X, shared = _batched_x(X, O)
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
+        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
+    if tuple(vchol.shape) != (O, M, M):
+        raise ValueError(f"chol_variational_covar must be {(O, M, M)}, got {tuple(vchol.shape)}")
+    if tuple(hyper.shape) != (O, 4 + 2 * D):
+        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+    return (X, shared, Z.detach().contiguous().float(), Linv.detach().contiguous(),
+            vmean.detach().reshape(O, M).contiguous().float(), vchol.detach().contiguous().float(),
+            hyper.detach().contiguous().float())
+
+
+def variational_chol_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                                     vchol: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
+                                     save: bool = False) -> VariationalCholOut:
+    """``variational_chol_forward`` for O outputs in one launch (gpk_variational_chol_batched_f32):
+    X (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64, vmean
+    (O, M), vchol (O, M, M), hyper (O, 4 + 2D) -> mean, var (O, B, N), one clamp flag word for all
+    outputs and, with ``save``, the O states. Bit-identical to O single-output calls."""
+    _require_device(X, Z, Linv, vmean, vchol, hyper)
+    X, shared, Z, Linv, vmean, vchol, hyper = _chol_batched_args(X, Z, Linv, vmean, vchol, hyper)
+    O, M, D = Z.shape
+    B, N = X.shape[-3], X.shape[-2]
+    dev = X.device
+    mean = torch.empty(O, B, N, device=dev, dtype=torch.float32)
+    var = torch.empty(O, B, N, device=dev, dtype=torch.float32)
+    flags = torch.zeros(1, device=dev, dtype=torch.int32) if want_flags else None
+    lib = _native.lib()
+    saved = None
+    if B > 0:
+        nsaved = lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D)
+        if nsaved == 0:
+            raise ValueError(f"gpk_variational_chol_batched_f32 does not support O={O}, B={B}, N={N}, M={M}, "
+                             f"D={D}")
+        if save:
+            saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_chol_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
+        hyper.data_ptr(), O, B, N, M, D, mean.data_ptr(), var.data_ptr(),
+        flags.data_ptr() if flags is not None else None, saved.data_ptr() if saved is not None else None,
+        _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_batched_f32")
+    return VariationalCholOut(mean, var, flags, saved)
+
+
+def variational_chol_adjoint_batched(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
+    """``variational_chol_adjoint`` for O outputs, every launch once
+    (gpk_variational_chol_adjoint_batched_f32) -> (dX (O, B, N, D) per output also with shared
+    inputs, dLinv (O, M, M) float64 lower, dZ (O, M, D), dpar (O, M + 2D + 2), dchol (O, M, M))."""
+    _require_device(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+    X, shared, Z, Linv, vmean, vchol, hyper = _chol_batched_args(X, Z, Linv.double(), vmean, vchol, hyper)
+    O, M, D = Z.shape
+    B, N = X.shape[-3], X.shape[-2]
+    dev = X.device
+    lib = _native.lib()
+    if saved.dtype != torch.float32 or saved.device != dev:
+        raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device})")
+    if saved.numel() * 4 != lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D):
+        raise ValueError("saved state does not match this shape (variational_chol_forward_batched(save=True))")
+    nbytes = lib.gpk_variational_chol_adjoint_batched_workspace_bytes(O, B, N, M, D)
+    if nbytes == 0:
+        raise ValueError(f"gpk_variational_chol_adjoint_batched_f32 does not support O={O}, B={B}, N={N}, "
+                         f"M={M}, D={D}")
+    gmean = gmean.detach().reshape(O, B, N).contiguous().float()
+    gvar = gvar.detach().reshape(O, B, N).contiguous().float()
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(O, M + 2 * D + 2, device=dev, dtype=torch.float32)
+    dchol = torch.empty(O, M, M, device=dev, dtype=torch.float32)
+    rc = lib.gpk_variational_chol_adjoint_batched_f32(
+        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
+        hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), saved.detach().contiguous().data_ptr(), O, B, N, M,
+        D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(),
+        _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_adjoint_batched_f32")
+    return dX, dLinv, dZ, dpar, dchol
+
+
+def _kl_batched_args(m, chol):
+    if m.dim() != 2 or tuple(chol.shape) != (m.shape[0], m.shape[1], m.shape[1]):
+        raise ValueError(f"m must be (O, M) and chol (O, M, M), got {tuple(m.shape)} and {tuple(chol.shape)}")
+    return m.detach().contiguous().float(), chol.detach().contiguous().float()
+
+
+def cholesky_kl_batched(m: torch.Tensor, chol: torch.Tensor) -> torch.Tensor:
+    """KL(N(m_o, L_o L_o^T) || N(0, I)), L_o = tril(chol_o), per output as an (O,) tensor (one launch)."""
+    _require_device(m, chol)
+    m, chol = _kl_batched_args(m, chol)
+    O, M = m.shape
+    kl = torch.empty(O, device=m.device, dtype=torch.float32)
+    rc = _native.lib().gpk_cholesky_kl_batched_f32(m.data_ptr(), chol.data_ptr(), O, M, kl.data_ptr(), None, None,
+                                                   None, _stream_ptr(m.device))
+    _native.check(rc, "gpk_cholesky_kl_batched_f32")
+    return kl
+
+
+def cholesky_kl_grad_batched(m, chol, gkl):
+    _require_device(m, chol, gkl)
+    m, chol = _kl_batched_args(m, chol)
+    O, M = m.shape
+    gkl = gkl.detach().reshape(O).contiguous().float()
+    dm = torch.empty_like(m)
+    dchol = torch.empty_like(chol)
+    rc = _native.lib().gpk_cholesky_kl_batched_f32(m.data_ptr(), chol.data_ptr(), O, M, None, gkl.data_ptr(),
+                                                   dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
+    _native.check(rc, "gpk_cholesky_kl_batched_f32")
+    return dm, dchol

@@ -235,3 +235,33 @@ def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mea
     if return_hyper:
         out += (hyper,)
     return out
+
+
+def variational_predict_chol_batched(x, Z, vmean, vchol, outputscale, lengthscale, mean_module, jitter,
+                                     cache: Optional[KzzCache] = None, key_tensors=None,
+                                     return_linv: bool = False):
+    """``variational_predict_batched`` for a Cholesky q(u) per output, N(vmean_o, L_o L_o^T) with
+    L_o = tril(vchol_o) (gpk::variational_chol_fwd_batched, one launch chain each way): x (B, N, D)
+    shared by the outputs or (O, B, N, D), Z (O, M, D), vmean (O, M), vchol (O, M, M) -> mean, var
+    (O, B, N), one clamp flag for all outputs (and Linv (O, M, M)). The same ``KzzCache`` entry for
+    the (O, M, M) factor, spent-marking and pending verdict as the mean-field sibling. The caller
+    has checked that the kernels serve the shape (ops.variational_chol_batched_supported)."""
+    O, M, D = Z.shape
+    w, b0 = _mean_params_batched(mean_module, O, D, x.device)
+    s2 = outputscale.reshape(O)
+    ls = lengthscale.reshape(O, -1)
+    vmean = vmean.reshape(O, M)
+    vchol = vchol.reshape(O, M, M)
+    if cache is None or key_tensors is None:
+        cache = KzzCache()
+        key_tensors = (Z, s2, ls)
+    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vchol, s2, ls, w, b0))
+    mean, var, flags, _, _ = torch.ops.gpk.variational_chol_fwd_batched(x, Linv, Z, vmean, vchol, s2, ls, w, b0,
+                                                                        float(jitter), save)
+    cache.note_consumers(mean, var)
+    cache.check_pending()
+    out = (mean, var, flags)
+    if return_linv:
+        out += (Linv,)
+    return out

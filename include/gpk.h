@@ -602,6 +602,59 @@ int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, con
                         float* dchol, void* stream);
 
 /*
+ * gpk_variational_chol_f32, its adjoint and gpk_cholesky_kl_f32 for O outputs at once (a
+ * multi-output layer with a Cholesky q(u): batch_shape [O] on the distribution, mean and kernel).
+ * The output index is grid dimension y of every launch; a workgroup offsets its base pointers by
+ * it and is otherwise the single-output workgroup at the same (B, N, M, D), so output o is
+ * bit-identical to a single-output call on output o's arrays. The single-output entry points are
+ * the O = 1 case of the same launchers. The chain stays seven launches and two memsets each way
+ * whatever O is (the zero-fill of the shared pipeline's dw / K_XX partials is one strided memset
+ * over the O slices each).
+ *   X : (B, N, D) read by every output when shared_x != 0 (DeepGPLayer's stride-0 expansion: no
+ *       (O, B, N, D) copy is made), else (O, B, N, D)
+ *   Z : (O, M, D)   Linv : (O, M, M) double   vmean : (O, M)   vchol : (O, M, M), lower read
+ *   hyp : (O, 4 + 2D)   mean, var : (O, B, N) float out
+ *   flags : (1,) int out or NULL: one word, every output ORs into it (the only atomic)
+ *   saved : NULL (inference) or gpk_variational_chol_batched_saved_bytes(O, B, N, M, D) bytes,
+ *       16-byte aligned: O slices of the single-output state; non-NULL at a shape whose saved size
+ *       is 0 is an argument error (-16)
+ *   gmean, gvar : (O, B, N)
+ *   workspace : gpk_variational_chol_adjoint_batched_workspace_bytes(O, B, N, M, D) bytes,
+ *       16-byte aligned: O slices of the single-output query. Each slice opens with the
+ *       gpk_variational_cov_grad_f32 plan; W diag(gvar) and the row partials follow it.
+ *   dX : (O, B, N, D) float out, per output also with shared inputs (the caller sums over O)
+ *   dLinv : (O, M, M) double out   dZ : (O, M, D) out   dpar : (O, M + 2D + 2) out
+ *   dchol : (O, M, M) out, lower, upper triangle zero
+ *   gpk_cholesky_kl_batched_f32: m (O, M), chol (O, M, M), kl and gkl (O,), dm (O, M),
+ *       dchol (O, M, M); one launch each way, output o on grid y.
+ * Both queries return O x the single-output value, 0 for a shape the single-output query refuses
+ * or O outside 1 .. 65535 (gridDim.y). Shape bounds are the single-output ones: M <= 256,
+ * D <= 64, and N <= 256 for the adjoint; B = 0 launches nothing. Every argument is validated
+ * before the first HIP call; an argument error is -(argument index).
+ *
+ * Replaces (reference): ToyDeepGPHiddenLayer(output_dims = O) (denoising_model/DeepGP.py:24-38)
+ * with upstream variational/cholesky_variational_distribution.py of batch_shape [O] through
+ * variational/variational_strategy.py forward and _variational_strategy.py::kl_divergence, and the
+ * autograd backward train.py:166 runs through them.
+ *
+ * Memory at O = 4: saved and workspace are 4 x the single-output figures above.
+ */
+size_t gpk_variational_chol_batched_saved_bytes(int O, int B, int N, int M, int D);
+int gpk_variational_chol_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                     const float* vmean, const float* vchol, const float* hyp, int O, int B,
+                                     int N, int M, int D, float* mean, float* var, int* flags, void* saved,
+                                     void* stream);
+size_t gpk_variational_chol_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D);
+int gpk_variational_chol_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                             const float* vmean, const float* vchol, const float* hyp,
+                                             const float* gmean, const float* gvar, const void* saved, int O,
+                                             int B, int N, int M, int D, void* workspace, float* dX,
+                                             double* dLinv, float* dZ, float* dpar, float* dchol,
+                                             void* stream);
+int gpk_cholesky_kl_batched_f32(const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
+                                float* dm, float* dchol, void* stream);
+
+/*
  * Batched Cholesky root of dense covariances, fused with sampling: per matrix b
  *   R R^T = cov[b] + jitter I        (lower factor, fp32, one workgroup, the matrix in LDS)
  *   samples[s, b, i] = mean[b, i] + sum_{j <= i} R[b, i, j] eps[s, b, j]   (ascending j)

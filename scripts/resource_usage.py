@@ -25,13 +25,14 @@ for line in r.stderr.splitlines():
     m = re.search(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\d+)", line)
     if m and cur is not None:
         cur[m.group(1).strip()] = int(m.group(2))
-print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'occ':>4s}")
+print(f"{'kernel':60s} {'VGPR':>5s} {'AGPR':>5s} {'vspill':>6s} {'sspill':>6s} {'occ':>4s} {'scratch':>7s} {'LDS':>6s}")
 for row in rows:
     n = row["name"]
     if flt and flt not in n:
         continue
     n = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", n)[:60]
     print(f"{n:60s} {row.get('VGPRs', 0):5d} {row.get('AGPRs', 0):5d} {row.get('VGPRs Spill', 0):6d} "
-          f"{row.get('SGPRs Spill', 0):6d} {row.get('Occupancy [waves/SIMD]', 0):4d}")
+          f"{row.get('SGPRs Spill', 0):6d} {row.get('Occupancy [waves/SIMD]', 0):4d} "
+          f"{row.get('ScratchSize [bytes/lane]', 0):7d} {row.get('LDS Size [bytes/block]', 0):6d}")
 if r.returncode:
     print(r.stderr[-3000:])
