@@ -133,6 +133,22 @@ SIGNATURES = {
                                                          c_void_p]),
     "gpk_cholesky_kl_batched_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),
+    "gpk_variational_chol_cov_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "gpk_variational_chol_cov_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "gpk_variational_chol_cov_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gpk_variational_chol_cov_batched_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                     c_void_p]),
+    "gpk_variational_chol_cov_grad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "gpk_variational_chol_cov_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_variational_chol_cov_grad_batched_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "gpk_variational_chol_cov_grad_batched_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p]),
     "gpk_mvn_root_max_n": (c_int, []),
     "gpk_mvn_root_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),

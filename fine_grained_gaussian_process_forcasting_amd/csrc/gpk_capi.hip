@@ -8,6 +8,7 @@
 #include "gpk_posterior_grad.h"
 #include "gpk_variational_cov_grad.h"
 #include "gpk_var_chol.h"
+#include "gpk_var_chol_cov.h"
 
 size_t gpk_mvn_root_refine_ws_floats(int B, int n);
 int gpk_launch_mvn_root_refine(const float* cov, const float* R, int B, int n, float jitter, float* ws,
@@ -788,6 +789,125 @@ int gpk_variational_chol_adjoint_batched_f32(const float* X, int shared_x, const
   GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
                       dX, dLinv, dZ, dpar, dchol, O, shared_x ? 0LL : (long long)B * N * D};
   return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
+}
+
+// ---- dense covariance of q(f) for a Cholesky q(u) and its adjoint (gpk_var_chol_cov.hip)
+size_t gpk_variational_chol_cov_workspace_bytes(int B, int N, int M) {
+  return gpk_var_chol_cov_state_bytes(B, N, M);
+}
+
+size_t gpk_variational_chol_cov_batched_workspace_bytes(int O, int B, int N, int M) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_var_chol_cov_state_bytes(B, N, M);
+}
+
+int gpk_variational_chol_cov_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
+                                 const float* hyp, int B, int N, int M, int D, void* workspace, float* cov,
+                                 void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vchol == nullptr) return -4;
+  if (hyp == nullptr) return -5;
+  if (B < 0) return -6;
+  if (N < 1) return -7;
+  if (M < 1 || M > 256) return -8;
+  if (D < 1 || D > 64) return -9;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -10;   // panel rows are read 16 B at a time
+  if (cov == nullptr) return -11;
+  if (gpk_var_chol_cov_state_bytes(B, N, M) == 0 && B > 0) return -7;
+  if (B == 0) return 0;
+  GpkVarCholCovArgs a{X, Z, Linv, vchol, hyp, B, N, M, D, 1, 0LL, (float*)workspace, cov};
+  return gpk_launch_var_chol_cov(a, (hipStream_t)stream);
+}
+
+int gpk_variational_chol_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                         const float* vchol, const float* hyp, int O, int B, int N, int M,
+                                         int D, void* workspace, float* cov, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vchol == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (O < 1 || O > kGpkMaxOutputs) return -7;
+  if (B < 0) return -8;
+  if (N < 1) return -9;
+  if (M < 1 || M > 256) return -10;
+  if (D < 1 || D > 64) return -11;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
+  if (cov == nullptr) return -13;
+  if (gpk_var_chol_cov_state_bytes(B, N, M) == 0 && B > 0) return -9;
+  if (B == 0) return 0;
+  GpkVarCholCovArgs a{X, Z, Linv, vchol, hyp, B, N, M, D, O, shared_x ? 0LL : (long long)B * N * D,
+                      (float*)workspace, cov};
+  return gpk_launch_var_chol_cov(a, (hipStream_t)stream);
+}
+
+size_t gpk_variational_chol_cov_grad_workspace_bytes(int B, int N, int M, int D) {
+  return gpk_var_chol_cov_grad_ws_bytes(B, N, M, D);
+}
+
+size_t gpk_variational_chol_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D) {
+  if (O < 1 || O > kGpkMaxOutputs) return 0;
+  return (size_t)O * gpk_var_chol_cov_grad_ws_bytes(B, N, M, D);
+}
+
+int gpk_variational_chol_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
+                                      const float* hyp, const void* state, const float* gcov, int B, int N,
+                                      int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
+                                      float* dpar, float* dchol, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -2;
+  if (Linv == nullptr) return -3;
+  if (vchol == nullptr) return -4;
+  if (hyp == nullptr) return -5;
+  if (state == nullptr || ((size_t)state & 15) != 0) return -6;
+  if (gcov == nullptr) return -7;
+  if (B < 0) return -8;
+  if (N < 1 || N > kGpkMvnRootMaxN) return -9;
+  if (M < 1 || M > 256) return -10;
+  if (D < 1 || D > 64) return -11;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
+  if (dX == nullptr) return -13;
+  if (dLinv == nullptr) return -14;
+  if (dZ == nullptr) return -15;
+  if (dpar == nullptr) return -16;
+  if (dchol == nullptr) return -17;
+  if (B > 0 && gpk_var_chol_cov_grad_ws_bytes(B, N, M, D) == 0) return -8;
+  if (B == 0) return 0;
+  GpkVarCholCovGradArgs a{X, Z, Linv, vchol, hyp, (const float*)state, gcov, B, N, M, D, 1, 0LL, workspace,
+                          dX, dLinv, dZ, dpar, dchol};
+  return gpk_launch_var_chol_cov_grad(a, (hipStream_t)stream);
+}
+
+int gpk_variational_chol_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                              const float* vchol, const float* hyp, const void* state,
+                                              const float* gcov, int O, int B, int N, int M, int D,
+                                              void* workspace, float* dX, double* dLinv, float* dZ,
+                                              float* dpar, float* dchol, void* stream) {
+  if (X == nullptr) return -1;
+  if (Z == nullptr) return -3;
+  if (Linv == nullptr) return -4;
+  if (vchol == nullptr) return -5;
+  if (hyp == nullptr) return -6;
+  if (state == nullptr || ((size_t)state & 15) != 0) return -7;
+  if (gcov == nullptr) return -8;
+  if (O < 1 || O > kGpkMaxOutputs) return -9;
+  if (B < 0) return -10;
+  if (N < 1 || N > kGpkMvnRootMaxN) return -11;
+  if (M < 1 || M > 256) return -12;
+  if (D < 1 || D > 64) return -13;
+  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
+  if (dX == nullptr) return -15;
+  if (dLinv == nullptr) return -16;
+  if (dZ == nullptr) return -17;
+  if (dpar == nullptr) return -18;
+  if (dchol == nullptr) return -19;
+  if (B > 0 && gpk_var_chol_cov_grad_ws_bytes(B, N, M, D) == 0) return -10;
+  if (B == 0) return 0;
+  GpkVarCholCovGradArgs a{X, Z, Linv, vchol, hyp, (const float*)state, gcov, B, N, M, D, O,
+                          shared_x ? 0LL : (long long)B * N * D, workspace, dX, dLinv, dZ, dpar, dchol};
+  return gpk_launch_var_chol_cov_grad(a, (hipStream_t)stream);
 }
 
 int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,

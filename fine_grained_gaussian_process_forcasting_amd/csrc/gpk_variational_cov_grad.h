@@ -38,3 +38,13 @@ int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream);
 size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, int* as);
 int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
                                     hipStream_t stream);
+
+// The same from a caller-supplied dA for an objective that does have a K_XX term (the dense
+// covariance of a Cholesky q(u), gpk_var_chol_cov.hip): q, dlinv, kxx, reduce, finish -- the
+// sequence of gpk_launch_var_cov_grad without t. kxx reads gcov and the windows' own means of
+// x / l: a.state is the caller's saved state, state_stride the floats between two outputs' states
+// and mu_offset the floats from an output's state to its means (B, 64) -- passed, not derived,
+// because a state that holds more than one panel puts them elsewhere (mu_offset >= B * M * as).
+// Only dw is zero-filled (dpar[0..M) comes out 0); ds2 / dlengthscale carry both parts.
+int gpk_launch_var_cov_grad_from_dA_kxx(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
+                                        long long state_stride, long long mu_offset, hipStream_t stream);

@@ -832,6 +832,39 @@ int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, size_t ws_stride
   return (int)hipGetLastError();
 }
 
+int gpk_launch_var_cov_grad_from_dA_kxx(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
+                                        long long state_stride, long long mu_offset, hipStream_t stream) {
+  vcg_set_lds_once();
+  if (!vcg_shape_ok(a.B, a.N, a.M, a.D) || a.O < 1 || a.O > 65535) return -9;
+  VcgArgs k{a, vcg_plan(a.B, a.N, a.M, a.D), state_stride, ws_stride, dpar_stride};
+  if (ws_stride < k.p.total || (ws_stride & 15) != 0 || dpar_stride < a.M + 1 + a.D) return -9;
+  // kxx finds a window's means B * M * as floats into an output's state: hand it the base that
+  // puts them at the caller's offset (it reads nothing else of the state)
+  const long long own = (long long)a.B * a.M * k.p.as;
+  if (a.state == nullptr || a.gcov == nullptr || mu_offset < own || state_stride < mu_offset + (long long)a.B * 64)
+    return -9;
+  k.a.state = a.state + (mu_offset - own);
+  const unsigned O = (unsigned)a.O;
+  const unsigned gq = (unsigned)(k.p.nchunk * k.p.ncb);
+  const size_t lds = vcg_q_lds(k.p.MP, k.p.Dq);
+  const long long nred = ((long long)a.M * a.M + (long long)k.p.MP * k.p.Dq + 255) / 256;
+  // what t would have written: no dw (kxx writes every K_XX partial itself)
+  const size_t ndw = (size_t)a.B * a.M * sizeof(float);
+  const hipError_t e = O == 1 ? hipMemsetAsync((char*)a.ws + k.p.off_dw, 0, ndw, stream)
+                              : hipMemset2DAsync((char*)a.ws + k.p.off_dw, ws_stride, 0, ndw, O, stream);
+  if (e != hipSuccess) return (int)e;
+  if (k.p.Dq == 16) hipLaunchKernelGGL(gpk_vcg_q_kernel<1>, dim3(gq, O), dim3(256), lds, stream, k);
+  else if (k.p.Dq == 32) hipLaunchKernelGGL(gpk_vcg_q_kernel<2>, dim3(gq, O), dim3(256), lds, stream, k);
+  else hipLaunchKernelGGL(gpk_vcg_q_kernel<4>, dim3(gq, O), dim3(256), lds, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_dlinv_kernel, dim3((unsigned)(k.p.npairs * k.p.nsplit), O), dim3(256), 0, stream, k);
+  if (k.p.Dq == 16) hipLaunchKernelGGL(gpk_vcg_kxx_kernel<1>, dim3(gq, O), dim3(256), 0, stream, k);
+  else if (k.p.Dq == 32) hipLaunchKernelGGL(gpk_vcg_kxx_kernel<2>, dim3(gq, O), dim3(256), 0, stream, k);
+  else hipLaunchKernelGGL(gpk_vcg_kxx_kernel<4>, dim3(gq, O), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_reduce_kernel, dim3((unsigned)nred, O), dim3(256), 0, stream, k);
+  hipLaunchKernelGGL(gpk_vcg_finish_kernel, dim3(1, O), dim3(256), 0, stream, k);
+  return (int)hipGetLastError();
+}
+
 int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream) {
   vcg_set_lds_once();
   if (!vcg_shape_ok(a.B, a.N, a.M, a.D)) return -9;

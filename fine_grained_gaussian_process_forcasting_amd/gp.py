@@ -782,6 +782,49 @@ def _variational_cov_grad_on_kernels(x, Z, Linv, vstd, outputscale, lengthscale)
     return _native.lib().gpk_variational_cov_grad_workspace_bytes(B, N, M, D) > 0
 
 
+def _chol_cov_kernel_inputs(x, Z, vchol) -> bool:
+    return (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32
+            and vchol.dtype == torch.float32 and x.numel() > 0)
+
+
+def _variational_chol_cov_on_kernels(x, Z, Linv, vchol, outputscale, lengthscale) -> bool:
+    """The dense covariance of q(f) with a Cholesky q(u) runs on gpk_variational_chol_cov_f32 when
+    no gradient can flow (grad mode off, or none of the tensors requires grad), the inputs are
+    CUDA fp32 and the workspace query accepts the shape (M <= 256, D <= 64); the differentiable
+    covariance is _variational_chol_cov_grad_on_kernels' case, and every CPU path stays
+    variational_chol_dense_covariance. Z (O, M, D): the batched form."""
+    if not _chol_cov_kernel_inputs(x, Z, vchol):
+        return False
+    if not _no_grad_flows(x, Z, Linv, vchol, outputscale, lengthscale):
+        return False
+    from . import _native
+    B, N, D = x.shape[-3:]
+    M = Z.shape[-2]
+    if D > 64:
+        return False
+    if Z.dim() == 3:
+        return _native.lib().gpk_variational_chol_cov_batched_workspace_bytes(Z.shape[0], B, N, M) > 0
+    return _native.lib().gpk_variational_chol_cov_workspace_bytes(B, N, M) > 0
+
+
+def _variational_chol_cov_grad_on_kernels(x, Z, Linv, vchol, outputscale, lengthscale) -> bool:
+    """The differentiable form runs on gpk::variational_chol_cov_train (the same forward keeping
+    its stacked [W; A] panels, its adjoint gpk_variational_chol_cov_grad_f32) when a gradient can
+    flow, the inputs are CUDA fp32 and the adjoint's workspace query accepts the shape (M <= 256,
+    D <= 64, N <= 256); variational_chol_dense_covariance stays for CPU tensors, other dtypes and
+    refused shapes. Z (O, M, D): the batched form, x (B, N, D) or (O, B, N, D)."""
+    if not _chol_cov_kernel_inputs(x, Z, vchol):
+        return False
+    if _no_grad_flows(x, Z, Linv, vchol, outputscale, lengthscale):
+        return False
+    from . import _native
+    B, N, D = x.shape[-3:]
+    M = Z.shape[-2]
+    if Z.dim() == 3:
+        return _native.lib().gpk_variational_chol_cov_grad_batched_workspace_bytes(Z.shape[0], B, N, M, D) > 0
+    return _native.lib().gpk_variational_chol_cov_grad_workspace_bytes(B, N, M, D) > 0
+
+
 class VariationalStrategy(nn.Module):
     """Whitened VariationalStrategy for one DeepGP layer (output_dims=None).
 
@@ -877,8 +920,13 @@ class VariationalStrategy(nn.Module):
         stride-0 expansion of the inputs is read in place (no (O, B, N, D) copy) and the per-output
         dLinv flow into one batched K_ZZ adjoint. Every other case -- a refused shape, another
         dtype, CPU tensors -- is variational_chol_predict in torch from the same shared K_ZZ factor
-        (KzzCache), one evaluation per output for a multi-output layer; the dense covariance behind
-        covariance_matrix / rsample is torch in every case."""
+        (KzzCache), one evaluation per output for a multi-output layer. The dense covariance behind
+        covariance_matrix / rsample is materialised on request: by gpk::variational_chol_cov when no
+        gradient can flow and gpk::variational_chol_cov_train with its HIP adjoint when one can (all
+        outputs of a multi-output layer on one launch chain; dLinv flows into the same Linv as the
+        marginals' and dchol to chol_variational_covar, so the layer still runs one K_ZZ adjoint per
+        step), and by variational_chol_dense_covariance in torch for CPU tensors, other dtypes and
+        shapes the queries refuse."""
         from .ops_autograd import (_mean_params, _mean_params_batched, variational_predict_chol,
                                    variational_predict_chol_batched)
         model = self.model
@@ -925,6 +973,16 @@ class VariationalStrategy(nn.Module):
                 self._kzz_cache.check_pending()
 
             def cov():
+                # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
+                xc = x[..., 0, :, :].reshape(-1, N, D) if (x.stride(-3) == 0 or O == 1) else xo
+                if _variational_chol_cov_on_kernels(xc, Z, Linv, vc, s2, ls):
+                    from .library import _cov_hyper
+                    hyper = _cov_hyper(xc, Z, s2, ls, float(jitter))
+                    c = torch.ops.gpk.variational_chol_cov(xc, Linv, Z, vc, hyper)     # (O, B', N, N)
+                    return c.reshape(O, *batch, N, N).movedim(0, -3)
+                if _variational_chol_cov_grad_on_kernels(xc, Z, Linv, vc, s2, ls):
+                    c = torch.ops.gpk.variational_chol_cov_train(xc, Linv, Z, vc, s2, ls, float(jitter))[0]
+                    return c.reshape(O, *batch, N, N).movedim(0, -3)
                 return torch.stack([variational_chol_dense_covariance(xo[o], Z[o], Linv[o], vc[o], s2[o], ls[o],
                                                                       jitter).reshape(*batch, N, N)
                                     for o in range(O)], dim=-3)
@@ -952,6 +1010,13 @@ class VariationalStrategy(nn.Module):
             self._kzz_cache.check_pending()
 
         def cov():
+            if _variational_chol_cov_on_kernels(xf, Z, Linv, vc, s2, ls):
+                from .library import _cov_hyper
+                hyper = _cov_hyper(xf, Z, s2.reshape(()), ls.reshape(-1), float(jitter))
+                return torch.ops.gpk.variational_chol_cov(xf, Linv, Z, vc, hyper).reshape(*batch, N, N)
+            if _variational_chol_cov_grad_on_kernels(xf, Z, Linv, vc, s2, ls):
+                return torch.ops.gpk.variational_chol_cov_train(
+                    xf, Linv, Z, vc, s2.reshape(()), ls.reshape(-1), float(jitter))[0].reshape(*batch, N, N)
             return variational_chol_dense_covariance(xf, Z, Linv, vc, s2, ls, jitter).reshape(*batch, N, N)
         return MultivariateNormal(mean.reshape(*batch, N), var.reshape(*batch, N), clamp_flag=flag,
                                   covar_fn=cov)

@@ -37,6 +37,12 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
                                                                                [autograd]
   gpk::variational_cov_grad(x, Linv, Z, vstd, hyper, state, gcov) -> (dX, dLinv, dZ, dpar)
       (both also for the O outputs of a multi-output layer: Z (O, M, D))
+  gpk::variational_chol_cov(x, Linv, Z, vchol, hyper) -> cov                  [eval only]
+  gpk::variational_chol_cov_train(x, Linv, Z, vchol, s2, ls, jitter) -> (cov, hyper, state)
+                                                                               [autograd]
+  gpk::variational_chol_cov_grad(x, Linv, Z, vchol, hyper, state, gcov)
+      -> (dX, dLinv, dZ, dpar, dchol)
+      (the three above for a Cholesky q(u); Z (M, D) or (O, M, D))
   gpk::mvn_root(cov, jitter, mean, eps, want_R) -> (R, samples, info)         [autograd]
   gpk::mvn_root_grad(R, gR, gsamples, eps) -> (dcov, dmean)
   gpk::mvn_root_refine(cov, jitter, R) -> R refined (the backward's factor when jitter > 0)
@@ -697,6 +703,98 @@ def _covt_backward(ctx, gcov, _ghyper, _gstate):
 
 
 variational_cov_train.register_autograd(_covt_backward, setup_context=_covt_setup)
+
+
+# The same three ops for a Cholesky q(u) (gpk_variational_chol_cov_f32 and its adjoint
+# gpk_variational_chol_cov_grad_f32): vchol = chol_variational_covar, (M, M) or (O, M, M).
+
+
+@torch.library.custom_op("gpk::variational_chol_cov", mutates_args=(), device_types="cuda")
+def variational_chol_cov(x: Tensor, Linv: Tensor, Z: Tensor, vchol: Tensor, hyper: Tensor) -> Tensor:
+    """Z (M, D): x (B, N, D) -> cov (B, N, N). Z (O, M, D), the outputs of a multi-output layer on
+    one launch chain: x (B, N, D) shared or (O, B, N, D) -> cov (O, B, N, N)."""
+    return ops.variational_chol_cov(x, Z, Linv, vchol, hyper)
+
+
+@variational_chol_cov.register_fake
+def _(x, Linv, Z, vchol, hyper):
+    B, N = x.shape[-3], x.shape[-2]
+    if Z.dim() == 3:
+        return x.new_empty(Z.shape[0], B, N, N)
+    return x.new_empty(B, N, N)
+
+
+@torch.library.custom_op("gpk::variational_chol_cov_train", mutates_args=(), device_types="cuda")
+def variational_chol_cov_train(x: Tensor, Linv: Tensor, Z: Tensor, vchol: Tensor, s2: Tensor, ls: Tensor,
+                               jitter: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """gpk::variational_chol_cov from the parameters, for a gradient: -> (cov, packed hyper, state).
+    The state is the forward's workspace (the stacked [W; A] panels in fp32 and the windows' means).
+    Z (O, M, D): the batched form, with s2 (O,), ls (O, D) or (O, 1), vchol (O, M, M) and x
+    (B, N, D) shared or (O, B, N, D)."""
+    hyper = _cov_hyper(x, Z, s2, ls, jitter)
+    cov, state = ops.variational_chol_cov(x, Z, Linv, vchol, hyper, return_state=True)
+    return cov, hyper, state
+
+
+def _chol_cov_state_numel(x, Z):
+    B, N = x.shape[-3], x.shape[-2]
+    if B == 0:
+        return 0
+    O = Z.shape[0] if Z.dim() == 3 else 1
+    return max(1, O * (_native.lib().gpk_variational_chol_cov_workspace_bytes(B, N, Z.shape[-2]) // 4))
+
+
+@variational_chol_cov_train.register_fake
+def _(x, Linv, Z, vchol, s2, ls, jitter):
+    B, N, D = x.shape[-3:]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        return x.new_empty(O, B, N, N), x.new_empty(O, 4 + 2 * D), x.new_empty(_chol_cov_state_numel(x, Z))
+    return x.new_empty(B, N, N), x.new_empty(4 + 2 * D), x.new_empty(_chol_cov_state_numel(x, Z))
+
+
+@torch.library.custom_op("gpk::variational_chol_cov_grad", mutates_args=(), device_types="cuda")
+def variational_chol_cov_grad(x: Tensor, Linv: Tensor, Z: Tensor, vchol: Tensor, hyper: Tensor, state: Tensor,
+                              gcov: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX, dLinv, dZ (the K_ZX part), dpar = [ds2, dls (D)], dchol); Z (O, M, D): every array
+    with a leading O, dX (O, B, N, D) per output also for shared inputs."""
+    return ops.variational_chol_cov_grad(x, Z, Linv, vchol, hyper, state, gcov)
+
+
+@variational_chol_cov_grad.register_fake
+def _(x, Linv, Z, vchol, hyper, state, gcov):
+    B, N, D = x.shape[-3:]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(O, 1 + D),
+                torch.empty_like(vchol))
+    return (torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(1 + D),
+            torch.empty_like(vchol))
+
+
+def _ccovt_setup(ctx, inputs, output):
+    x, Linv, Z, vchol, s2, ls, jitter = inputs
+    ctx.save_for_backward(x, Linv, Z, vchol, s2, ls, output[1], output[2])
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+@torch.autograd.function.once_differentiable
+def _ccovt_backward(ctx, gcov, _ghyper, _gstate):
+    x, Linv, Z, vchol, s2, ls, hyper, state = ctx.saved_tensors
+    dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_cov_grad(x, Linv, Z, vchol, hyper, state,
+                                                                         gcov.contiguous())
+    dls = dpar[..., 1:]
+    if Z.dim() == 3:
+        O = Z.shape[0]
+        if x.dim() == 3:
+            dX = dX.sum(0)                      # inputs shared by the outputs
+        dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
+    else:
+        dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
+    return (dX, dLinv, dZ, dchol.reshape(vchol.shape), dpar[..., 0].reshape(s2.shape), dls, None)
+
+
+variational_chol_cov_train.register_autograd(_ccovt_backward, setup_context=_ccovt_setup)
 
 
 @torch.library.custom_op("gpk::mvn_root", mutates_args=(), device_types="cuda")

@@ -1554,3 +1554,116 @@ def cholesky_kl_grad_batched(m, chol, gkl):
                                                    dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
     _native.check(rc, "gpk_cholesky_kl_batched_f32")
     return dm, dchol
+
+
+# ---------------------------------------------------------------------------
+# Dense covariance of q(f) for a Cholesky q(u): gpk_variational_chol_cov_f32 / _grad_f32 and their
+# batched forms (Z (M, D): one output; Z (O, M, D): O outputs on one launch chain)
+# ---------------------------------------------------------------------------
+def _chol_cov_args(X, Z, Linv, vchol, hyper):
+    """Checked, contiguous arguments -> (X, shared, Z, Linv, vchol, hyper, O or None, B, N, M, D)."""
+    _require_device(X, Z, Linv, vchol, hyper)
+    if Z.dim() == 3:
+        O, M, D = Z.shape
+        X, shared = _batched_x(X, O)
+        lead = (O,)
+    elif Z.dim() == 2:
+        O, (M, D) = None, Z.shape
+        if X.dim() != 3:
+            raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
+        X, shared, lead = X.detach().contiguous().float(), True, ()
+    else:
+        raise ValueError(f"Z must be (M, D) or (O, M, D), got {tuple(Z.shape)}")
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (..., M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if tuple(Linv.shape) != lead + (M, M) or Linv.dtype != torch.float64:
+        raise ValueError(f"Linv must be {lead + (M, M)} float64 from kzz_cholesky")
+    if tuple(vchol.shape) != lead + (M, M):
+        raise ValueError(f"chol_variational_covar must be {lead + (M, M)}, got {tuple(vchol.shape)}")
+    if tuple(hyper.shape) != lead + (4 + 2 * D,):
+        raise ValueError(f"hyper must be {lead + (4 + 2 * D,)}, got {tuple(hyper.shape)}")
+    return (X, shared, Z.detach().contiguous().float(), Linv.detach().contiguous(),
+            vchol.detach().contiguous().float(), hyper.detach().contiguous().float(), O, B, N, M, D)
+
+
+def variational_chol_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vchol: torch.Tensor,
+                         hyper: torch.Tensor, return_state: bool = False):
+    """Dense covariance of q(f) with a Cholesky q(u): K_XX + jitter I + W^T W - A^T A, A = Linv K_ZX,
+    W = tril(vchol)^T A (two gfx950 launches, include/gpk.h::gpk_variational_chol_cov_f32). Z (M, D):
+    X (B, N, D) -> cov (B, N, N). Z (O, M, D): X (B, N, D) shared or (O, B, N, D), every other array
+    with a leading O -> cov (O, B, N, N), output o bit-identical to a single-output call.
+    ``return_state``: -> (cov, workspace), the stacked [W; A] panels and window means that
+    ``variational_chol_cov_grad`` runs from (2 B M N floats, N rounded up to 64, per output)."""
+    X, shared, Z, Linv, vchol, hyper, O, B, N, M, D = _chol_cov_args(X, Z, Linv, vchol, hyper)
+    dev = X.device
+    lib = _native.lib()
+    if O is None:
+        nbytes = lib.gpk_variational_chol_cov_workspace_bytes(B, N, M)
+    else:
+        nbytes = lib.gpk_variational_chol_cov_batched_workspace_bytes(O, B, N, M)
+    if (nbytes == 0 and B > 0) or D > 64:
+        raise ValueError(f"gpk_variational_chol_cov_f32 does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+    cov = torch.empty(*(() if O is None else (O,)), B, N, N, device=dev, dtype=torch.float32)
+    if B == 0:
+        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    if O is None:
+        rc = lib.gpk_variational_chol_cov_f32(X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(),
+                                              hyper.data_ptr(), B, N, M, D, ws.data_ptr(), cov.data_ptr(),
+                                              _stream_ptr(dev))
+    else:
+        rc = lib.gpk_variational_chol_cov_batched_f32(
+            X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(), O, B,
+            N, M, D, ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_cov_f32")
+    return (cov, ws) if return_state else cov
+
+
+def variational_chol_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vchol: torch.Tensor,
+                              hyper: torch.Tensor, state: torch.Tensor, gcov: torch.Tensor):
+    """Adjoint of ``variational_chol_cov`` (include/gpk.h::gpk_variational_chol_cov_grad_f32): from
+    gcov = dObjective / dcov (any matrix per window) and the forward's workspace ``state`` ->
+    (dX, dLinv float64 lower, dZ (the K_ZX part), dpar = [ds2, dlengthscale (D)], dchol lower).
+    Z (O, M, D): every array with a leading O, dX (O, B, N, D) per output also with shared inputs
+    (the caller sums over O). M <= 256, D <= 64, N <= 256."""
+    X, shared, Z, Linv, vchol, hyper, O, B, N, M, D = _chol_cov_args(X, Z, Linv, vchol, hyper)
+    _require_device(state, gcov)
+    dev = X.device
+    lead = () if O is None else (O,)
+    if tuple(gcov.shape) != lead + (B, N, N):
+        raise ValueError(f"gcov must be {lead + (B, N, N)}, got {tuple(gcov.shape)}")
+    gcov = gcov.detach().contiguous().float()
+    lib = _native.lib()
+    if O is None:
+        nbytes = lib.gpk_variational_chol_cov_grad_workspace_bytes(B, N, M, D)
+        nstate = lib.gpk_variational_chol_cov_workspace_bytes(B, N, M)
+    else:
+        nbytes = lib.gpk_variational_chol_cov_grad_batched_workspace_bytes(O, B, N, M, D)
+        nstate = lib.gpk_variational_chol_cov_batched_workspace_bytes(O, B, N, M)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_variational_chol_cov_grad_f32 does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+    dX = torch.empty(*lead, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(*lead, 1 + D, device=dev, dtype=torch.float32)
+    dchol = torch.empty(*lead, M, M, device=dev, dtype=torch.float32)
+    if B == 0:
+        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_(), dchol.zero_()
+    if state.dtype != torch.float32 or state.device != dev or state.numel() != max(1, nstate // 4):
+        raise ValueError(f"state must be the {nstate // 4} float32 values on {dev} that "
+                         f"variational_chol_cov(return_state=True) returned for this shape")
+    state = state.detach().contiguous()
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    if O is None:
+        rc = lib.gpk_variational_chol_cov_grad_f32(
+            X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(), state.data_ptr(),
+            gcov.data_ptr(), B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(),
+            dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
+    else:
+        rc = lib.gpk_variational_chol_cov_grad_batched_f32(
+            X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
+            state.data_ptr(), gcov.data_ptr(), O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(),
+            dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, "gpk_variational_chol_cov_grad_f32")
+    return dX, dLinv, dZ, dpar, dchol

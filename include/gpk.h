@@ -655,6 +655,78 @@ int gpk_cholesky_kl_batched_f32(const float* m, const float* chol, int O, int M,
                                 float* dm, float* dchol, void* stream);
 
 /*
+ * Dense covariance of q(f) for a Cholesky q(u) (gpk_variational_chol_f32's distribution) and its
+ * adjoint. Per window b, with A = Linv K_ZX exactly as gpk_variational_cov_f32 forms it (fp32 Gram,
+ * fp64 MFMA solve, cast to fp32) and L_q = tril(C) (the strict upper triangle of C is never read,
+ * a diagonal entry may be negative):
+ *   W   = L_q^T A                                    (M, N), fp32 MFMA
+ *   cov = K_XX + jitter I + W^T W - A^T A            diag: s2 + jitter + sum_m W_mi^2 - sum_m A_mi^2
+ * (unclamped: the 1e-6 floor of gpk_variational_chol_f32 belongs to .variance). Two launches on
+ * `stream`: phase 1, one workgroup per (window, 64-point block), writes the stacked panel
+ * S = [W; A] as (B, 2 M, as) floats, as = N rounded up to 64, and then the window's own mean of
+ * x / l (B, 64) into the workspace; phase 2 is the SYRK S^T diag(+1, -1) S of
+ * gpk_variational_cov_f32's phase 2 over the 2 M rows: cov[i][j] == cov[j][i] bitwise, the
+ * diagonal from the same accumulators. The workspace is the adjoint's saved state.
+ *
+ * The adjoint, for g = dObjective / dcov (any (N, N) matrix per window), H = g + g^T:
+ *   T = S H = [T_W; T_A]     dA = L_q T_W - T_A     dchol = tril(sum_b A T_W^T)   (lower, upper zero)
+ * and from dA on exactly gpk_variational_cov_grad_f32 (dLinv, Q and the RBF tail of K_ZX, P = H o
+ * K_XX): its q / dlinv / kxx / reduce / finish kernels run on the dA materialised in their
+ * workspace. Eight launches and one memset on `stream`, no host synchronisation, no atomics in any
+ * sum, fixed summation orders in fp64: two calls give the same bits; a window's cov and dX depend
+ * on that window alone. The jitter has no gradient.
+ *
+ * Replaces (reference): upstream variational/variational_strategy.py forward's predictive_covar
+ * with variational/cholesky_variational_distribution.py's q(u), evaluated densely by
+ * MultivariateNormal.covariance_matrix / rsample (denoising_model/DeepGP.py:62-64 ``x.rsample()``),
+ * and the autograd backward train.py:166 runs through it.
+ *
+ * Memory per call: workspace / saved state = gpk_variational_chol_cov_workspace_bytes(B, N, M) =
+ * (2 B M as + 64 B) * 4 bytes; the adjoint's workspace =
+ * gpk_variational_chol_cov_grad_workspace_bytes(B, N, M, D): the gpk_variational_cov_grad_f32
+ * workspace + 2 B M as floats of T + min(B, 32) M^2 doubles of dchol partials. Both queries return
+ * 0 for a shape that is not served.
+ *
+ * X : (B, N, D) float   Z : (M, D) float   Linv : (M, M) double   vchol : (M, M) float, row-major,
+ * lower read only   hyp : gpk_variational_f32's vector (s2, jitter and the lengthscales are read)
+ * workspace : device memory of the queried size, 16-byte aligned   cov : (B, N, N) float out
+ * state : the workspace the forward filled for the same arguments, 16-byte aligned
+ * gcov : (B, N, N) float   dX : (B, N, D) float out   dLinv : (M, M) double out, lower, upper zero
+ * dZ : (M, D) float out (the K_ZX part)   dpar : (1 + D) float out = {ds2, dlengthscale[D]}
+ * dchol : (M, M) float out, lower, upper zero
+ * Forward: M <= 256, D <= 64, N >= 1, B >= 0. Adjoint: additionally N <= 256 (the shared
+ * pipeline). B = 0 launches nothing.
+ *
+ * The batched calls run O outputs with o on grid dimension y of every launch: X (B, N, D) read by
+ * every output when shared_x != 0, else (O, B, N, D); a leading dense O on Z, Linv, vchol, hyp,
+ * the workspace / state (O slices of the single-output query), cov, gcov, dLinv, dZ, dpar, dchol
+ * and dX ((O, B, N, D) also with shared inputs: the caller sums over O). Output o is bit-identical
+ * to a single-output call on o's arrays; the single-output entry points are the O = 1 case of the
+ * same launchers. The batched queries return O x the single-output value, 0 for a refused shape
+ * or O outside 1 .. 65535. Every argument is validated before the first HIP call; an argument
+ * error is -(argument index).
+ */
+size_t gpk_variational_chol_cov_workspace_bytes(int B, int N, int M);
+int gpk_variational_chol_cov_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
+                                 const float* hyp, int B, int N, int M, int D, void* workspace, float* cov,
+                                 void* stream);
+size_t gpk_variational_chol_cov_batched_workspace_bytes(int O, int B, int N, int M);
+int gpk_variational_chol_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                         const float* vchol, const float* hyp, int O, int B, int N, int M,
+                                         int D, void* workspace, float* cov, void* stream);
+size_t gpk_variational_chol_cov_grad_workspace_bytes(int B, int N, int M, int D);
+int gpk_variational_chol_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
+                                      const float* hyp, const void* state, const float* gcov, int B, int N,
+                                      int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
+                                      float* dpar, float* dchol, void* stream);
+size_t gpk_variational_chol_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D);
+int gpk_variational_chol_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                              const float* vchol, const float* hyp, const void* state,
+                                              const float* gcov, int O, int B, int N, int M, int D,
+                                              void* workspace, float* dX, double* dLinv, float* dZ,
+                                              float* dpar, float* dchol, void* stream);
+
+/*
  * Batched Cholesky root of dense covariances, fused with sampling: per matrix b
  *   R R^T = cov[b] + jitter I        (lower factor, fp32, one workgroup, the matrix in LDS)
  *   samples[s, b, i] = mean[b, i] + sum_{j <= i} R[b, i, j] eps[s, b, j]   (ascending j)
