@@ -44,6 +44,23 @@ SIGNATURES = {
     "gpk_exact_posterior_grad_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # per-window hyper-parameters: the sibling's list plus hyp_stride after n_lengthscale
+    "gpk_exact_mll_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_int,
+                                         c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p]),
+    "gpk_exact_mll_grad_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                              c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
+    "gpk_exact_posterior_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
+                                               c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p]),
+    "gpk_exact_posterior_cov_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                   ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_exact_posterior_grad_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                                    ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_chol_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_double, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_backward_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -35,13 +35,20 @@ const char* gpk_strerror(int code) {
 
 int gpk_exact_max_n(void) { return kGpkExactMaxN; }
 
-int gpk_exact_mll_f32(const float* X, const float* y, const float* hyp, int n_lengthscale,
-                      int B, int N, int D, double jitter, int max_tries, float* L, float* z,
-                      float* mll, int* info, void* stream) {
+// hyp_stride of the *_perwin_f32 entry points: 0 (one hyper vector for every window) or at least
+// the vector's length.
+static bool hyp_stride_ok(long long hyp_stride, int n_lengthscale) {
+  return hyp_stride == 0 || hyp_stride >= 3 + (long long)n_lengthscale;
+}
+
+int gpk_exact_mll_perwin_f32(const float* X, const float* y, const float* hyp, int n_lengthscale,
+                             long long hyp_stride, int B, int N, int D, double jitter, int max_tries,
+                             float* L, float* z, float* mll, int* info, void* stream) {
   if (X == nullptr) return -1;
   if (y == nullptr) return -2;
   if (hyp == nullptr) return -3;
   if (n_lengthscale != 1 && n_lengthscale != D) return -4;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -5;
   if (B < 0) return -5;
   if (N < 1) return -6;
   if (D < 1) return -7;
@@ -53,9 +60,16 @@ int gpk_exact_mll_f32(const float* X, const float* y, const float* hyp, int n_le
   if (N > kGpkExactRegMaxN && L == nullptr) return -10;   // the blocked path factors in L
   if (N > kGpkExactRegMaxN && D > 64) return -7;
   if (B == 0) return 0;
-  GpkExactArgs a{X, y, hyp, n_lengthscale, B, N, D, jitter, max_tries, L, z, mll, info};
+  GpkExactArgs a{X, y, hyp, n_lengthscale, B, N, D, jitter, max_tries, L, z, mll, info, hyp_stride};
   if (N > kGpkExactRegMaxN) return gpk_launch_exact_large(a, (hipStream_t)stream);
   return gpk_launch_exact(a, (hipStream_t)stream);
+}
+
+int gpk_exact_mll_f32(const float* X, const float* y, const float* hyp, int n_lengthscale,
+                      int B, int N, int D, double jitter, int max_tries, float* L, float* z,
+                      float* mll, int* info, void* stream) {
+  return gpk_exact_mll_perwin_f32(X, y, hyp, n_lengthscale, 0, B, N, D, jitter, max_tries, L, z, mll, info,
+                                  stream);
 }
 
 size_t gpk_exact_grad_workspace_bytes(int B, int N) {
@@ -64,14 +78,16 @@ size_t gpk_exact_grad_workspace_bytes(int B, int N) {
   return gpk_exact_grad_ws_floats(B, N) * sizeof(float);
 }
 
-int gpk_exact_mll_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
-                           int n_lengthscale, int B, int N, int D, const float* gout, void* workspace,
-                           float* dX, float* dy, float* dhyp, void* stream) {
+int gpk_exact_mll_grad_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                  int n_lengthscale, long long hyp_stride, int B, int N, int D,
+                                  const float* gout, void* workspace, float* dX, float* dy, float* dhyp,
+                                  void* stream) {
   if (X == nullptr) return -1;
   if (L == nullptr) return -2;
   if (z == nullptr) return -3;
   if (hyp == nullptr) return -4;
   if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -6;
   if (B < 0) return -6;
   if (N < 1 || N > gpk_exact_max_n()) return -7;
   if (D < 1 || D > 64) return -8;
@@ -79,19 +95,27 @@ int gpk_exact_mll_grad_f32(const float* X, const float* L, const float* z, const
   if (workspace == nullptr && B > 0 && gpk_exact_grad_workspace_bytes(B, N) > 0) return -10;
   if (dhyp == nullptr) return -13;
   if (B == 0) return 0;
-  GpkExactGradArgs a{X, L, z, hyp, n_lengthscale, B, N, D, gout, (float*)workspace, dX, dy, dhyp};
+  GpkExactGradArgs a{X, L, z, hyp, n_lengthscale, B, N, D, gout, (float*)workspace, dX, dy, dhyp, hyp_stride};
   if (N > kGpkExactRegMaxN) return gpk_launch_exact_large_grad(a, (hipStream_t)stream);
   return gpk_launch_exact_grad(a, (hipStream_t)stream);
 }
 
-int gpk_exact_posterior_f32(const float* X, const float* L, const float* z, const float* hyp,
-                            int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
-                            float* mean, float* var, void* stream) {
+int gpk_exact_mll_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
+                           int n_lengthscale, int B, int N, int D, const float* gout, void* workspace,
+                           float* dX, float* dy, float* dhyp, void* stream) {
+  return gpk_exact_mll_grad_perwin_f32(X, L, z, hyp, n_lengthscale, 0, B, N, D, gout, workspace, dX, dy, dhyp,
+                                       stream);
+}
+
+int gpk_exact_posterior_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                   int n_lengthscale, long long hyp_stride, const float* Xs, int B, int N,
+                                   int Ns, int D, float* mean, float* var, void* stream) {
   if (X == nullptr) return -1;
   if (L == nullptr) return -2;
   if (z == nullptr) return -3;
   if (hyp == nullptr) return -4;
   if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -6;
   if (Xs == nullptr) return -6;
   if (B < 0) return -7;
   if (N < 1 || N > gpk_exact_max_n()) return -8;
@@ -100,9 +124,15 @@ int gpk_exact_posterior_f32(const float* X, const float* L, const float* z, cons
   if (mean == nullptr) return -11;
   if (var == nullptr) return -12;
   if (B == 0 || Ns == 0) return 0;
-  GpkPostArgs a{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var};
+  GpkPostArgs a{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var, hyp_stride};
   if (N > kGpkExactRegMaxN) return gpk_launch_exact_large_posterior(a, (hipStream_t)stream);
   return gpk_launch_exact_posterior(a, (hipStream_t)stream);
+}
+
+int gpk_exact_posterior_f32(const float* X, const float* L, const float* z, const float* hyp,
+                            int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
+                            float* mean, float* var, void* stream) {
+  return gpk_exact_posterior_perwin_f32(X, L, z, hyp, n_lengthscale, 0, Xs, B, N, Ns, D, mean, var, stream);
 }
 
 size_t gpk_exact_posterior_cov_workspace_bytes(int B, int N, int Ns) {
@@ -111,14 +141,16 @@ size_t gpk_exact_posterior_cov_workspace_bytes(int B, int N, int Ns) {
   return gpk_post_cov_ws_floats(B, N, Ns) * sizeof(float);
 }
 
-int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, const float* hyp,
-                                int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
-                                void* workspace, float* mean, float* var, float* cov, void* stream) {
+int gpk_exact_posterior_cov_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                       int n_lengthscale, long long hyp_stride, const float* Xs, int B, int N,
+                                       int Ns, int D, void* workspace, float* mean, float* var, float* cov,
+                                       void* stream) {
   if (X == nullptr) return -1;
   if (L == nullptr) return -2;
   if (z == nullptr) return -3;
   if (hyp == nullptr) return -4;
   if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -6;
   if (Xs == nullptr) return -6;
   if (B < 0) return -7;
   if (N < 1 || N > gpk_exact_max_n()) return -8;
@@ -134,15 +166,22 @@ int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, 
   float* V = (float*)workspace;
   float* mu = V + (size_t)B * N * vs;   // after V: the workspace layout of gpk_posterior_cov.h
   GpkPostVArgs a{};
-  static_cast<GpkPostArgs&>(a) = GpkPostArgs{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var};
+  static_cast<GpkPostArgs&>(a) = GpkPostArgs{X, L, z, hyp, n_lengthscale, Xs, B, N, Ns, D, mean, var, hyp_stride};
   a.V = V;
   a.mu = mu;
   a.vs = vs;
   const int rc = N > kGpkExactRegMaxN ? gpk_launch_exact_large_posterior_storev(a, (hipStream_t)stream)
                                       : gpk_launch_exact_posterior_storev(a, (hipStream_t)stream);
   if (rc != 0) return rc;
-  GpkPostCovArgs c{hyp, n_lengthscale, Xs, V, mu, var, B, N, Ns, D, vs, cov};
+  GpkPostCovArgs c{hyp, n_lengthscale, Xs, V, mu, var, B, N, Ns, D, vs, cov, hyp_stride};
   return gpk_launch_exact_posterior_cov(c, (hipStream_t)stream);
+}
+
+int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                int n_lengthscale, const float* Xs, int B, int N, int Ns, int D,
+                                void* workspace, float* mean, float* var, float* cov, void* stream) {
+  return gpk_exact_posterior_cov_perwin_f32(X, L, z, hyp, n_lengthscale, 0, Xs, B, N, Ns, D, workspace, mean, var,
+                                            cov, stream);
 }
 
 // ---- adjoint of the exact posterior (gpk_posterior_grad.hip)
@@ -150,16 +189,17 @@ size_t gpk_exact_posterior_grad_workspace_bytes(int B, int N, int Ns, int D) {
   return gpk_post_grad_ws_bytes(B, N, Ns, D);
 }
 
-int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
-                                 int n_lengthscale, const float* Xs, const float* state,
-                                 const float* gmean, const float* gvar, const float* gcov,
-                                 int B, int N, int Ns, int D, void* workspace,
-                                 float* dX, float* dy, float* dXs, float* dhyp, void* stream) {
+int gpk_exact_posterior_grad_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                        int n_lengthscale, long long hyp_stride, const float* Xs,
+                                        const float* state, const float* gmean, const float* gvar,
+                                        const float* gcov, int B, int N, int Ns, int D, void* workspace,
+                                        float* dX, float* dy, float* dXs, float* dhyp, void* stream) {
   if (X == nullptr) return -1;
   if (L == nullptr) return -2;
   if (z == nullptr) return -3;
   if (hyp == nullptr) return -4;
   if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -6;
   if (Xs == nullptr) return -6;
   if (state == nullptr || ((size_t)state & 15) != 0) return -7;   // V rows are read 16 B at a time
   if (gmean == nullptr && gvar == nullptr && gcov == nullptr) return -8;
@@ -172,8 +212,17 @@ int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z,
   if (B > 0 && gpk_post_grad_ws_bytes(B, N, Ns, D) == 0) return -11;
   if (B == 0) return 0;
   GpkPostGradArgs a{X, L, z, hyp, n_lengthscale, Xs, state, gmean, gvar, gcov, B, N, Ns, D, workspace,
-                    dX, dy, dXs, dhyp};
+                    dX, dy, dXs, dhyp, hyp_stride};
   return gpk_launch_exact_posterior_grad(a, (hipStream_t)stream);
+}
+
+int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                 int n_lengthscale, const float* Xs, const float* state,
+                                 const float* gmean, const float* gvar, const float* gcov,
+                                 int B, int N, int Ns, int D, void* workspace,
+                                 float* dX, float* dy, float* dXs, float* dhyp, void* stream) {
+  return gpk_exact_posterior_grad_perwin_f32(X, L, z, hyp, n_lengthscale, 0, Xs, state, gmean, gvar, gcov, B, N,
+                                             Ns, D, workspace, dX, dy, dXs, dhyp, stream);
 }
 
 int gpk_kzz_chol_f64(const float* Z, const float* hyp, int M, int D, float jitter,

@@ -200,7 +200,7 @@ GPK_DEVICE void grad_solve_body(const GpkExactGradArgs& a, float* smem) {
   const float* Lb = a.L + (size_t)b * N * N;
   const GradWs ws = grad_ws(N);
   float* wsb = a.ws + (size_t)b * ws.per;
-  const float* hyp = a.hyp;
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
   const int n_ls = a.n_ls;
 
   // ---- prologue: diagonal blocks of L (staged in stg), z, column sums of x / l
@@ -526,7 +526,7 @@ __global__ void __launch_bounds__(64 * kGW, DQ == 4 ? 4 : 8) gpk_grad_gram_kerne
   const int b = blockIdx.x;
   const float* Xb = a.X + (size_t)b * N * D;
   const float* wsb = a.ws + (size_t)b * ws.per;
-  const float* hyp = a.hyp;
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
   const bool ard = a.n_ls > 1;
   float* xs = smem;                  // NP x XS
   float* nrm = xs + NP * XS;         // NP
@@ -699,7 +699,7 @@ GPK_DEVICE void grad_gram_split_body(const GpkExactGradArgs& a, float* smem) {
   const int b = blockIdx.x;
   const float* Xb = a.X + (size_t)b * N * D;
   const float* wsb = a.ws + (size_t)b * ws.per;
-  const float* hyp = a.hyp;
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
   const bool ard = a.n_ls > 1;
   // xs = x / l - mean -> split planes (rows: dims 0..DW-1, zero padded; columns: dims < DP)
   for (int base = 0; base < NP * DW; base += 4 * 64 * kGW) {
@@ -941,7 +941,7 @@ __global__ void __launch_bounds__(128) gpk_grad_fin_kernel(GpkExactGradArgs a, i
   const float* wsb = a.ws + (size_t)b * ws.per;
   const float* part = wsb + ws.part;
   float* o = a.dhyp + (size_t)b * (3 + a.n_ls);
-  const float* hyp = a.hyp;
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
   // thread t < 64: dl_t (t < D); 64: ds2, 65: dnoise, 66: dc
   const int f = t < 64 ? (t < D ? 2 + t : -1) : (t == 64 ? 0 : (t == 65 ? 1 : -1));
   float s = 0.f;

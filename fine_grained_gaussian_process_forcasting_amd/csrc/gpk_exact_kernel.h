@@ -1236,10 +1236,11 @@ GPK_DEVICE int exact_role(int p) {
 template <int NB, int W, bool STAMPS, bool FULL, int OCC = 2>
 __global__ void __launch_bounds__(64 * W, (OCC * W) / 4)
 gpk_exact_kernel(const float* __restrict__ X, const float* __restrict__ y,
-                 const float* __restrict__ hyp, int n_ls, int N_in, int D, int DC,
+                 const float* __restrict__ hyp_all, int n_ls, int N_in, int D, int DC,
                  double jitter0, int max_tries, float* __restrict__ Lout,
                  float* __restrict__ zout, float* __restrict__ mll,
-                 int* __restrict__ info, unsigned long long* __restrict__ stamps = nullptr) {
+                 int* __restrict__ info, unsigned long long* __restrict__ stamps = nullptr,
+                 long long hyp_stride = 0) {
   constexpr int NT = ExactPlan<NB>::NT;
   const int N = FULL ? 16 * NB : N_in;  // FULL: no padded rows anywhere
   // DIAG_ALONE (small-batch layout, 16 waves, NB <= 8): the diagonal wave gets a SIMD to
@@ -1280,6 +1281,9 @@ gpk_exact_kernel(const float* __restrict__ X, const float* __restrict__ y,
   const int DP = DC * 16;
   const int NP = NB * 16;
 
+  // this window's hyper vector (hyp_stride 0: one shared by every window); block-uniform, so
+  // the reads below stay scalar loads
+  const float* __restrict__ hyp = hyp_all + (long long)b * hyp_stride;
   const float s2u = hyp[0];
   const float noise = hyp[1];
   const float cmean = hyp[2];
@@ -1921,7 +1925,7 @@ int launch_exact_w(const GpkExactArgs& a, unsigned long long* stamps, hipStream_
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((gpk_exact_kernel<NB, W, STAMPS, FULL, OCC>), dim3(a.B), dim3(64 * W), lds, stream,
                      a.X, a.y, a.hyp, a.n_ls, a.N, a.D, DC, a.jitter, a.max_tries,
-                     a.L, a.z, a.mll, a.info, stamps);
+                     a.L, a.z, a.mll, a.info, stamps, a.hyp_stride);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
 }

@@ -249,10 +249,11 @@ __global__ void __launch_bounds__(kLgThreads, 1) gpk_lg_exact_kernel(GpkExactArg
   const float* X = a.X + (size_t)b * N * D;
   const float* y = a.y + (size_t)b * N;
   float* Lg = a.L + (size_t)b * N * N;
-  const float s2 = a.hyp[0], noise = a.hyp[1], cmean = a.hyp[2];
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  const float s2 = hyp[0], noise = hyp[1], cmean = hyp[2];
   const int g = lane >> 4, c = lane & 15, q = lane >> 4, il = lane & 15;
 
-  lg_centre(X, a.hyp, a.n_ls, N, Np, D, mu, ils, nrm, panel, tid, kLgThreads);
+  lg_centre(X, hyp, a.n_ls, N, Np, D, mu, ils, nrm, panel, tid, kLgThreads);
   // the strict upper triangle of L is zero and never touched again
   for (int i = wave; i < N; i += kLgWaves)
     for (int j = i + 1 + lane; j < N; j += 64) Lg[(size_t)i * N + j] = 0.f;
@@ -526,7 +527,8 @@ __global__ void __launch_bounds__(kLgThreads, 1) gpk_lg_grad_kernel(GpkExactGrad
   float* Kw = Xw + (size_t)Np * Np;             // K_hat^-1 (lower 16x16 tiles)
   const int g = lane >> 4, c = lane & 15, q = lane >> 4, il = lane & 15;
 
-  lg_centre(X, a.hyp, a.n_ls, N, Np, D, mu, ils, nrm, smem + lay.scr, tid, kLgThreads);
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  lg_centre(X, hyp, a.n_ls, N, Np, D, mu, ils, nrm, smem + lay.scr, tid, kLgThreads);
   for (int i = tid; i < Np; i += kLgThreads) zb[i] = i < N ? a.z[(size_t)b * N + i] : 0.f;
   // ---- 1. diagonal-block inverses X_kk = L_kk^-1
   for (int k = wave; k < nb; k += kLgWaves) {
@@ -661,7 +663,7 @@ __global__ void __launch_bounds__(kLgThreads, 1) gpk_lg_grad_kernel(GpkExactGrad
   //      G = g (alpha alpha^T - K_hat^-1) / (2N), E = K / s2, W = G o K (zero diagonal)
   const float gout = a.gout[b];
   const float gsc = gout / (2.f * (float)N);
-  const float s2 = a.hyp[0];
+  const float s2 = hyp[0];
   const int nDQ = (D + 15) / 16;
   // the hyper-parameter sums cancel heavily (sum G o E of a well-fit model is ~1e-3 of its
   // terms): fp64 accumulators, fixed-order reduction
@@ -808,10 +810,11 @@ __global__ void __launch_bounds__(kPostThreads) gpk_lg_post_kernel(GpkPostArgsOf
   const float* X = a.X + (size_t)b * N * D;
   const float* Xs = a.Xs + (size_t)b * Ns * D;
   const float* Lg = a.L + (size_t)b * N * N;
-  const float s2 = a.hyp[0], cmean = a.hyp[2];
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  const float s2 = hyp[0], cmean = hyp[2];
   const int g = lane >> 4, c = lane & 15, q = lane >> 4, il = lane & 15;
 
-  lg_centre(X, a.hyp, a.n_ls, N, Np, D, mu, ils, nrm, V, tid, kPostThreads);
+  lg_centre(X, hyp, a.n_ls, N, Np, D, mu, ils, nrm, V, tid, kPostThreads);
   if constexpr (STOREV) {
     if (blockIdx.x == 0 && tid < D) a.mu[(size_t)b * 64 + tid] = mu[tid];
   }

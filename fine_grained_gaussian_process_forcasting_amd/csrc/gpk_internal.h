@@ -14,6 +14,7 @@ struct GpkExactArgs {
   float* z;            // (B, N) or nullptr: L^{-1}(y - c)
   float* mll;          // (B,)
   int* info;           // (B,)
+  long long hyp_stride = 0;  // floats between two windows' hyper vectors; 0 = one vector shared by all
 };
 
 int gpk_launch_exact(const GpkExactArgs& a, hipStream_t stream);
@@ -30,6 +31,7 @@ struct GpkExactGradArgs {
   float* dX;           // (B, N, D) or nullptr
   float* dy;           // (B, N) or nullptr
   float* dhyp;         // (B, 3 + n_ls): per-window d/d{s2, noise, c, lengthscale...}
+  long long hyp_stride = 0;  // as GpkExactArgs
 };
 
 size_t gpk_exact_grad_ws_floats(int B, int N);
@@ -133,6 +135,7 @@ struct GpkPostArgs {
   int B, N, Ns, D;
   float* mean;         // (B, Ns) posterior mean of f
   float* var;          // (B, Ns) posterior variance of f (unclamped)
+  long long hyp_stride = 0;  // as GpkExactArgs
 };
 
 size_t gpk_post_lds_bytes(int N, int D);

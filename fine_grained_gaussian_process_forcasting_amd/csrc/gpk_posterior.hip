@@ -80,9 +80,10 @@ __global__ __launch_bounds__(256) void gpk_post_kernel(GpkPostArgsOf<STOREV> a) 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c = lane & 15, g = lane >> 4;
 
-  const float s2 = a.hyp[0];
-  const float c0 = a.hyp[2];
-  const float* ls = a.hyp + 3;
+  const float* hyp = a.hyp + (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  const float s2 = hyp[0];
+  const float c0 = hyp[2];
+  const float* ls = hyp + 3;
   const bool ard = a.n_ls > 1;
   float* xtr = smem + lay.xtr;
   float* nrm = smem + lay.nrm;

@@ -37,6 +37,7 @@ struct GpkPostCovArgs {
   const float* var;    // (B, Ns) phase 1's variance: the diagonal of cov
   int B, N, Ns, D, vs;
   float* cov;          // (B, Ns, Ns) out
+  long long hyp_stride = 0;  // as GpkExactArgs
 };
 int gpk_launch_exact_posterior_cov(const GpkPostCovArgs& a, hipStream_t stream);
 

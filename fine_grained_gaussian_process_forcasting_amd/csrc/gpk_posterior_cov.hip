@@ -88,6 +88,7 @@ __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkCovArgsOf<VAR> a) 
     wstd = a.vstd + o * (size_t)N;
     vs = a.as;
   } else {
+    hyp += (long long)b * a.hyp_stride;  // this window's hyper vector (stride 0: shared)
     Xs = a.Xs + (size_t)b * Ns * D;
     Vb = a.V + (size_t)b * N * a.vs;
     mup = a.mu;

@@ -21,6 +21,7 @@ struct GpkPostGradArgs {
   float* dy;             // (B, N) out or nullptr
   float* dXs;            // (B, Ns, D) out or nullptr
   float* dhyp;           // (B, 3 + n_ls) out: per-window d/d{s2, noise, c, lengthscale...}
+  long long hyp_stride = 0;  // floats between two windows' hyper vectors; 0 = one vector shared by all
 };
 
 // 0 for a shape the kernels do not take (1 <= N, Ns <= 256, 1 <= D <= 64).

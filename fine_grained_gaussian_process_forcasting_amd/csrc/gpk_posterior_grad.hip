@@ -270,7 +270,8 @@ __global__ __launch_bounds__(256) void gpk_pg_ks_kernel(PgArgs k) {
   const int J = 64 * cb;
   const bool hasH = k.a.gvar != nullptr || k.a.gcov != nullptr;
   const bool hasM = k.a.gmean != nullptr;
-  const float s2 = k.a.hyp[0];
+  const float* hyp = k.a.hyp + (long long)b * k.a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  const float s2 = hyp[0];
   const float* Xb = k.a.X + (size_t)b * N * D;
   const float* Xsb = k.a.Xs + (size_t)b * Ns * D;
   const float* mup = k.a.state + (size_t)k.a.B * N * vs + (size_t)b * 64;
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(256) void gpk_pg_ks_kernel(PgArgs k) {
 
   if (tid < 64) {
     mu[tid] = tid < D ? mup[tid] : 0.f;
-    lsc[tid] = tid < D ? k.a.hyp[3 + (k.a.n_ls > 1 ? tid : 0)] : 1.f;
+    lsc[tid] = tid < D ? hyp[3 + (k.a.n_ls > 1 ? tid : 0)] : 1.f;
     const bool ok = hasM && J + tid < Ns;
     const float v = hasM ? k.a.gmean[(size_t)b * Ns + (ok ? J + tid : 0)] : 0.f;
     gm[tid] = ok ? v : 0.f;
@@ -472,7 +473,8 @@ __global__ __launch_bounds__(256) void gpk_pg_sq_kernel(PgArgs k) {
   const int I = 64 * rt;
   const bool hasH = k.a.gvar != nullptr || k.a.gcov != nullptr;
   const bool hasM = k.a.gmean != nullptr;
-  const float s2 = k.a.hyp[0];
+  const float* hyp = k.a.hyp + (long long)b * k.a.hyp_stride;  // this window's hyper vector (stride 0: shared)
+  const float s2 = hyp[0];
   const float* Pb = HAT ? k.a.X + (size_t)b * N * D : k.a.Xs + (size_t)b * Ns * D;
   const float* mup = k.a.state + (size_t)k.a.B * N * vs + (size_t)b * 64;
   const float* Wb = pg_ws(k, k.p.off_W) + (size_t)b * N * vs;
@@ -485,7 +487,7 @@ __global__ __launch_bounds__(256) void gpk_pg_sq_kernel(PgArgs k) {
 
   if (tid < 64) {
     mu[tid] = tid < D ? mup[tid] : 0.f;
-    lsc[tid] = tid < D ? k.a.hyp[3 + (k.a.n_ls > 1 ? tid : 0)] : 1.f;
+    lsc[tid] = tid < D ? hyp[3 + (k.a.n_ls > 1 ? tid : 0)] : 1.f;
     if constexpr (HAT) {   // without gmean, u and alpha were never computed and are not read
       ui[tid] = 0.f;
       ai[tid] = 0.f;
@@ -628,6 +630,7 @@ __global__ __launch_bounds__(256) void gpk_pg_finish_kernel(PgArgs k) {
   __shared__ float lsc[64], mu[64];
   const int N = k.a.N, Ns = k.a.Ns, D = k.a.D, Dq = k.p.Dq, vs = k.p.vs, n_ls = k.a.n_ls;
   const int tid = threadIdx.x, b = blockIdx.x;
+  const float* hyp = k.a.hyp + (long long)b * k.a.hyp_stride;  // this window's hyper vector (stride 0: shared)
   const bool hasH = k.a.gvar != nullptr || k.a.gcov != nullptr;
   const bool hasM = k.a.gmean != nullptr;
   const float* Xb = k.a.X + (size_t)b * N * D;
@@ -639,7 +642,7 @@ __global__ __launch_bounds__(256) void gpk_pg_finish_kernel(PgArgs k) {
   float* dh = k.a.dhyp + (size_t)b * (3 + n_ls);
   if (tid < 64) {
     mu[tid] = tid < D ? k.a.state[(size_t)k.a.B * N * vs + (size_t)b * 64 + tid] : 0.f;
-    lsc[tid] = tid < D ? k.a.hyp[3 + (n_ls > 1 ? tid : 0)] : 1.f;
+    lsc[tid] = tid < D ? hyp[3 + (n_ls > 1 ? tid : 0)] : 1.f;
   }
   __syncthreads();
   if (k.a.dX)
@@ -698,7 +701,7 @@ __global__ __launch_bounds__(256) void gpk_pg_finish_kernel(PgArgs k) {
     for (int rt = 0; rt < k.p.nrt; ++rt) { sq += (double)cp[4 + rt]; tr += (double)cp[8 + rt]; }
     if (hasH)
       for (int cb = 0; cb < k.p.ncb; ++cb) { sq += (double)cp[12 + cb]; trh += (double)cp[16 + cb]; }
-    dh[0] = (float)(sq / (double)k.a.hyp[0] + tr + trh);
+    dh[0] = (float)(sq / (double)hyp[0] + tr + trh);
     dh[1] = (float)tr;
     dh[2] = (float)sh[0];
   }

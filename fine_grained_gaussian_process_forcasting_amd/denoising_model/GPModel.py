@@ -22,6 +22,15 @@ returns the posterior there.
 
 Inputs may be batched (B, N, D) windows, a single (N, D) window or 1-D (N,) points,
 as GPyTorch accepts; targets follow (B, N) / (N,).
+
+Hyper-parameters: by default ONE set {outputscale, noise, constant, lengthscale} shared by the B
+windows (the reference's model). ``ExactGPModel(train_x, train_y, likelihood, batch_shape=
+torch.Size([B]))`` with ``GaussianLikelihood(batch_shape=torch.Size([B]))`` is GPyTorch's
+batch-independent exact GP: every window owns its set (``mean_module.constant`` (B, 1),
+``raw_outputscale`` (B,), ``raw_lengthscale`` (B, 1, n), ``raw_noise`` (B, 1)), the B sets travel
+as one (B, 3 + n_ls) matrix and every call is still one launch each way
+(include/gpk.h, the *_perwin_f32 entry points). A shared likelihood with a batched model (or the
+other way round) is a mixed model and works the same way.
 """
 from __future__ import annotations
 
@@ -33,7 +42,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..errors import GPInputWarning
-from ..gp import ConstantMean, MultivariateNormal, RBFKernel, ScaleKernel, psd_safe_cholesky
+from ..gp import ConstantMean, MultivariateNormal, RBFKernel, ScaleKernel, _per_window, psd_safe_cholesky
 
 
 def _as_batch(x: torch.Tensor) -> torch.Tensor:
@@ -65,21 +74,42 @@ def _version_key(*ts):
 
 
 class ExactGPModel(nn.Module):
-    def __init__(self, train_x, train_y, likelihood):
+    def __init__(self, train_x, train_y, likelihood, batch_shape=torch.Size([]), ard_num_dims=None):
         super().__init__()
+        batch_shape = torch.Size(batch_shape)
+        if len(batch_shape) > 1:
+            raise ValueError(f"batch_shape must be [] or [B], got {tuple(batch_shape)}")
+        self.batch_shape = batch_shape
+        self._check_windows(train_x)
         self.train_inputs = (train_x,)
         self.train_targets = train_y
         self.likelihood = likelihood
-        self.mean_module = ConstantMean()
-        self.covar_module = ScaleKernel(RBFKernel())
+        if len(batch_shape) == 0 and ard_num_dims is None:
+            self.mean_module = ConstantMean()
+            self.covar_module = ScaleKernel(RBFKernel())
+        else:
+            self.mean_module = ConstantMean(batch_shape=batch_shape)
+            self.covar_module = ScaleKernel(RBFKernel(ard_num_dims=ard_num_dims, batch_shape=batch_shape),
+                                            batch_shape=batch_shape)
         self._prediction_cache = None
         self._cache_handle = _PredictionCacheHandle(self)
         from ..ops_autograd import register_cache
         register_cache(self._cache_handle)
 
+    def _check_windows(self, x):
+        """A batch-independent model owns one hyper-parameter set per window: its batch_shape [B]
+        must be the windows of the inputs."""
+        if len(self.batch_shape) == 0 or x is None:
+            return
+        windows = _as_batch(x).shape[:1]
+        if windows != self.batch_shape:
+            raise RuntimeError(f"batch_shape {tuple(self.batch_shape)} does not match the windows of the inputs: "
+                               f"inputs of shape {tuple(x.shape)} hold {tuple(windows)} window(s)")
+
     def set_train_data(self, inputs=None, targets=None, strict=True):
         if inputs is not None:
             x = inputs[0] if isinstance(inputs, (tuple, list)) else inputs
+            self._check_windows(x)
             if strict and x.shape != self.train_inputs[0].shape:
                 raise RuntimeError("Cannot modify the shape of train inputs with strict=True")
             self.train_inputs = (x,)
@@ -94,6 +124,7 @@ class ExactGPModel(nn.Module):
         return super().train(mode)
 
     def forward(self, x):
+        self._check_windows(x)
         xb = _as_batch(x)
         mean_x = self.mean_module(x if x.dim() > 1 else x.unsqueeze(-1))
         return MultivariateNormal(mean_x, None,
@@ -112,10 +143,33 @@ class ExactGPModel(nn.Module):
         return self._posterior(x)
 
     # ---- eval mode -------------------------------------------------------------
-    def _hyper(self, device):
+    def _per_window(self) -> bool:
+        """Whether any hyper-parameter carries a window dimension (the model's batch_shape [B], or a
+        batched likelihood on a shared model)."""
         kern = self.covar_module
+        B = _as_batch(self.train_inputs[0]).shape[0]
+        return ops.exact_hyper_per_window(kern.raw_outputscale, self.likelihood.noise_covar.raw_noise,
+                                          self.mean_module.constant, kern.base_kernel.raw_lengthscale, B)
+
+    def _hyper(self, device):
+        """The packed hyper-parameters, detached: (3 + n_ls,) shared, or (B, 3 + n_ls) per window."""
+        kern = self.covar_module
+        if self._per_window():
+            B = _as_batch(self.train_inputs[0]).shape[0]
+            return ops.pack_exact_hyper_windows(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
+                                                kern.base_kernel.lengthscale, B).detach().to(device).contiguous()
         return ops.pack_exact_hyper(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
                                     kern.base_kernel.lengthscale, device)
+
+    def _hyper_live(self):
+        """The same, built differentiably (dhyp reaches the parameters through the constraints)."""
+        kern = self.covar_module
+        if self._per_window():
+            B = _as_batch(self.train_inputs[0]).shape[0]
+            return ops.pack_exact_hyper_windows(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
+                                                kern.base_kernel.lengthscale, B)
+        return ops.pack_exact_hyper_live(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
+                                         kern.base_kernel.lengthscale)
 
     def _train_factor(self):
         train_x, train_y = self.train_inputs[0], self.train_targets
@@ -135,6 +189,7 @@ class ExactGPModel(nn.Module):
         return entry
 
     def _posterior(self, x):
+        self._check_windows(x)
         params = [p for p in self.parameters()] + [x, self.train_inputs[0], self.train_targets]
         if torch.is_grad_enabled() and any(t.requires_grad for t in params):
             if self._grad_on_kernels(x):
@@ -191,10 +246,8 @@ class ExactGPModel(nn.Module):
         xs = _as_batch(x)
         if xs.shape[0] != Xb.shape[0]:
             xs = xs.expand(Xb.shape[0], *xs.shape[1:])
-        kern = self.covar_module
         # pack_exact_hyper's layout, but not detached (it detaches): dhyp must reach the parameters
-        hyper = ops.pack_exact_hyper_live(kern.outputscale, self.likelihood.noise, self.mean_module.constant,
-                                          kern.base_kernel.lengthscale)
+        hyper = self._hyper_live()
         mean, var, cov, _L, _z, _state, info = torch.ops.gpk.exact_posterior_train(
             Xb.contiguous(), yb.contiguous(), hyper, xs.contiguous(), 1e-6, 3)
         ops.check_cholesky_info(info, 1e-6, inputs=(Xb, yb))
@@ -225,10 +278,16 @@ class ExactGPModel(nn.Module):
         if xs.shape[0] != Xb.shape[0]:
             xs = xs.expand(Xb.shape[0], *xs.shape[1:])
         kern = self.covar_module
-        ls = kern.base_kernel.lengthscale.reshape(-1)
-        s2 = kern.outputscale.reshape(())
-        c = self.mean_module.constant.reshape(())
-        noise = self.likelihood.noise.reshape(())
+        B = Xb.shape[0]
+
+        def hyp(t, shared, min_dim=1):
+            # a per-window hyper-parameter (leading size B) broadcasts over its window's matrix
+            return t.reshape(B, 1, -1) if _per_window(t, B, min_dim) else t.reshape(shared)
+
+        ls = hyp(kern.base_kernel.lengthscale, (-1,), 2)
+        s2 = hyp(kern.outputscale, ())
+        c = hyp(self.mean_module.constant, ())
+        noise = hyp(self.likelihood.noise, ())
         n = Xb.shape[-2]
         full = torch.cat([Xb, xs], -2) / ls
         a = full - full.mean(-2, keepdim=True)
@@ -239,9 +298,9 @@ class ExactGPModel(nn.Module):
         Kxx = K[..., :n, :n] * (1.0 - eye) + s2 * eye        # exact diagonal, as _sq_dist zeroes it
         L = psd_safe_cholesky(Kxx + noise * eye)
         V = torch.linalg.solve_triangular(L, K[..., :n, n:], upper=False)
-        zz = torch.linalg.solve_triangular(L, (yb - c).unsqueeze(-1), upper=False)
-        mean = c + (V * zz).sum(-2)
-        var = s2 - (V * V).sum(-2)
+        zz = torch.linalg.solve_triangular(L, yb.unsqueeze(-1) - c, upper=False)
+        mean = (c + (V * zz).sum(-2, keepdim=True)).squeeze(-2)
+        var = (s2 - (V * V).sum(-2, keepdim=True)).squeeze(-2)
         if x.dim() == 3 or Xb.shape[0] > 1:
             shape = mean.shape
         else:

@@ -216,6 +216,15 @@ class MultivariateNormal:
     def event_shape(self):
         return self._mean.shape[-1:]
 
+    def _over_points(self, t):
+        """A hyper-parameter against the (..., N) marginals: one value, or one per window (the
+        batch entries of the mean) as (..., 1)."""
+        if not torch.is_tensor(t) or t.numel() == 1:
+            return t.reshape(()) if torch.is_tensor(t) else t
+        if t.numel() == self._mean.shape[:-1].numel():
+            return t.reshape(*self._mean.shape[:-1], 1)
+        return t
+
     @property
     def variance(self):
         if self._variance is None:
@@ -223,11 +232,12 @@ class MultivariateNormal:
                 raise NotImplementedError("this distribution carries no variance")
             # exact-GP prior: diag K(x, x) = outputscale (the RBF is 1 on the diagonal), as
             # GPyTorch's lazy kernel diagonal returns it
-            var = self._exact[2].reshape(()).expand(self._mean.shape)
+            # (a per-window outputscale (B,) of a batch-independent model: one value per window)
+            var = self._over_points(self._exact[2]).expand(self._mean.shape)
         else:
             var = self._variance
         if self._added_noise is not None:
-            var = var + self._added_noise
+            var = var + self._over_points(self._added_noise)
         min_var = settings.min_variance.value(var.dtype)
         if self._preclamped and self._added_noise is None:
             # a point slice of a kernel output: a clamped entry is exactly min_var
@@ -275,8 +285,10 @@ class MultivariateNormal:
         else:
             K = self._covar_fn()
         if self._added_noise is not None:
-            K = K + torch.diag_embed(torch.as_tensor(self._added_noise, dtype=K.dtype, device=K.device)
-                                     .expand(K.shape[:-1]))
+            noise = torch.as_tensor(self._added_noise, dtype=K.dtype, device=K.device)
+            if _per_window(noise, K.shape[0]):
+                noise = noise.reshape(-1, 1)          # (B, 1): one noise per window
+            K = K + torch.diag_embed(noise.expand(K.shape[:-1]))
         n = self._mean.shape[-1]
         if K.numel() != self._mean.numel() * n:   # an expanded distribution: its batch is a view
             K = K.expand(*self._mean.shape, n)
@@ -334,7 +346,18 @@ class MultivariateNormal:
             if X.numel() != self.batch_shape.numel() * n * d:
                 raise NotImplementedError("expand of an exact prior whose inputs do not follow its batch")
             Xe = X.reshape(*self.batch_shape, n, d).expand(*batch_size, n, d).reshape(-1, n, d)
-            exact = (Xe,) + tuple(exact[1:])
+            # per-window hyper-parameters (a batch-independent model) follow their windows
+            nb, ne = self.batch_shape.numel(), Xe.shape[0]
+
+            def follow(t, min_dim=1):
+                if not _per_window(t, nb, min_dim):
+                    return t
+                rest = t.shape[1:]
+                return t.reshape(*self.batch_shape, *rest).expand(*batch_size, *rest).reshape(ne, *rest)
+
+            exact = (Xe, follow(exact[1], 2)) + tuple(follow(t) for t in exact[2:])
+            noise = follow(self._added_noise)
+            return MultivariateNormal(mean, var, exact, noise, self._clamp_flag, self._preclamped, self._covar_fn)
         return MultivariateNormal(mean, var, exact, self._added_noise, self._clamp_flag,
                                   self._preclamped, self._covar_fn)
 
@@ -395,18 +418,30 @@ class MultivariateNormal:
         return res.reshape(value.shape[:-1])      # (N,) targets of an unbatched model -> scalar
 
 
+def _per_window(t, B: int, min_dim: int = 1) -> bool:
+    """Whether a hyper-parameter carries a window dimension: a tensor whose leading size is the
+    B > 1 windows ((B,), (B, 1); the lengthscale, ``min_dim`` 2: (B, 1, n)), as the parameters of a
+    batch-independent model (batch_shape = [B]) have. A shared one holds 1 (n) values, leading size 1."""
+    return torch.is_tensor(t) and B > 1 and t.dim() >= min_dim and t.shape[0] == B
+
+
 def rbf_covariance(X: torch.Tensor, lengthscale, outputscale) -> torch.Tensor:
     """outputscale * exp(-||x_i - x_j||^2 / (2 l^2)) for X (B, N, D), as GPyTorch's
     ScaleKernel(RBFKernel) evaluates a lazy kernel tensor (upstream kernels/rbf_kernel.py,
     kernel.py ``_sq_dist``: inputs divided by the lengthscale and centred by their mean,
-    ||a||^2 + ||b||^2 - 2 a.b clamped at 0, the x1 == x2 diagonal set to exactly 0)."""
-    ls = torch.as_tensor(lengthscale, device=X.device, dtype=X.dtype).reshape(-1)
+    ||a||^2 + ||b||^2 - 2 a.b clamped at 0, the x1 == x2 diagonal set to exactly 0).
+    Per-window hyper-parameters: lengthscale (B, 1, n) and / or outputscale (B,) give window b
+    its own kernel."""
+    B = X.shape[0] if X.dim() == 3 else 1
+    ls = torch.as_tensor(lengthscale, device=X.device, dtype=X.dtype)
+    ls = ls.reshape(B, 1, -1) if _per_window(ls, B, 2) else ls.reshape(-1)
     xs = X / ls
     xs = xs - xs.mean(-2, keepdim=True)
     nrm = xs.pow(2).sum(-1)
     d = (nrm.unsqueeze(-1) + nrm.unsqueeze(-2) - 2.0 * xs @ xs.transpose(-1, -2)).clamp_min(0.0)
     d = d * (1.0 - torch.eye(X.shape[-2], device=X.device, dtype=X.dtype))
-    s2 = torch.as_tensor(outputscale, device=X.device, dtype=X.dtype).reshape(())
+    s2 = torch.as_tensor(outputscale, device=X.device, dtype=X.dtype)
+    s2 = s2.reshape(B, 1, 1) if _per_window(s2, B) else s2.reshape(())
     return s2 * torch.exp(-0.5 * d)
 
 
@@ -594,7 +629,9 @@ class GaussianLikelihood(nn.Module):
 
     def forward(self, function_dist: MultivariateNormal) -> MultivariateNormal:
         """Marginal p(y) = q(f) + noise (only the diagonal is ever read on this path)."""
-        return function_dist.add_noise(self.noise.reshape(()))
+        noise = self.noise
+        # batch_shape [B]: one noise per window, (B, 1) against the (B, N) marginals
+        return function_dist.add_noise(noise.reshape(()) if noise.numel() == 1 else noise)
 
     def expected_log_prob(self, target: torch.Tensor, input: MultivariateNormal) -> torch.Tensor:
         mean, variance = input.mean, input.variance

@@ -6,6 +6,7 @@ to the dispatcher (FakeTensor shape propagation, ``torch.library.opcheck``, trac
 instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
 ``torch.cuda.current_stream()`` (ops.py); nothing here computes on the CPU.
 
+  (every exact op: hyper is (3 + n_ls,) shared by the B windows, or (B, 3 + n_ls), one row per window)
   gpk::exact_mll(X, y, hyper, jitter, max_tries) -> (mll, L, z, info)         [autograd]
   gpk::exact_mll_grad(X, L, z, hyper, gout) -> (dX, dy, dhyp)
   gpk::exact_posterior(X, L, z, hyper, Xs) -> (mean, var)                     [eval only]
@@ -97,7 +98,7 @@ def exact_mll_grad(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor,
 @exact_mll_grad.register_fake
 def _(X, L, z, hyper, gout):
     B, N, D = X.shape
-    return X.new_empty(B, N, D), X.new_empty(B, N), X.new_empty(B, hyper.numel())
+    return X.new_empty(B, N, D), X.new_empty(B, N), X.new_empty(B, hyper.shape[-1])
 
 
 @torch.library.custom_op("gpk::exact_posterior", mutates_args=(), device_types="cuda")
@@ -167,7 +168,13 @@ def exact_posterior_grad(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor, Xs: Ten
 @exact_posterior_grad.register_fake
 def _(X, L, z, hyper, Xs, state, gmean=None, gvar=None, gcov=None):
     B, N, D = X.shape
-    return X.new_empty(B, N, D), X.new_empty(B, N), torch.empty_like(Xs), X.new_empty(B, hyper.numel())
+    return X.new_empty(B, N, D), X.new_empty(B, N), torch.empty_like(Xs), X.new_empty(B, hyper.shape[-1])
+
+
+def _dhyper(dhyp, hyper):
+    """The kernels' per-window dhyp (B, 3 + n_ls) as the gradient of ``hyper``: its rows when hyper
+    is (B, 3 + n_ls), one row per window; their sum when every window shares one vector."""
+    return dhyp if hyper.dim() == 2 else dhyp.sum(0)
 
 
 def _post_train_setup(ctx, inputs, output):
@@ -185,7 +192,7 @@ def _post_train_backward(ctx, gmean, gvar, gcov, _gL, _gz, _gstate, _ginfo):
         return None, None, None, None, None, None
     gmean, gvar, gcov = (g.contiguous() if g is not None else None for g in (gmean, gvar, gcov))
     dX, dy, dXs, dhyp = torch.ops.gpk.exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov)
-    return dX, dy, dhyp.sum(0), dXs, None, None
+    return dX, dy, _dhyper(dhyp, hyper), dXs, None, None
 
 
 exact_posterior_train.register_autograd(_post_train_backward, setup_context=_post_train_setup)
@@ -203,7 +210,7 @@ def _exact_backward(ctx, gmll, _gL, _gz, _ginfo):
     if L.numel() == 0:
         raise RuntimeError("gpk::exact_mll was called with want_factor=False; no backward")
     dX, dy, dhyp = torch.ops.gpk.exact_mll_grad(X, L, z, hyper, gmll.contiguous())
-    return dX, dy, dhyp.sum(0), None, None, None
+    return dX, dy, _dhyper(dhyp, hyper), None, None, None
 
 
 exact_mll.register_autograd(_exact_backward, setup_context=_exact_setup)

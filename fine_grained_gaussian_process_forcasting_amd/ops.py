@@ -51,6 +51,68 @@ def pack_exact_hyper_live(outputscale, noise, mean_constant, lengthscale) -> tor
                       lengthscale.reshape(-1)]).float()
 
 
+def _hyper_piece(v, B: int, width: int, name: str, device=None) -> torch.Tensor:
+    """One hyper-parameter as (B, width): shared (``width`` values in any shape: expanded over the
+    windows, so autograd sums its gradient over them) or per-window (leading size B)."""
+    if not isinstance(v, torch.Tensor):
+        v = torch.full((1,), float(v), device=device, dtype=torch.float32)
+    if v.numel() == width:
+        return v.reshape(1, width).expand(B, width)
+    if v.dim() >= 1 and v.shape[0] == B and v.numel() == B * width:
+        return v.reshape(B, width)
+    raise ValueError(f"{name} must hold {width} shared value(s) or have a leading window dimension "
+                     f"B = {B} with {width} value(s) per window, got shape {tuple(v.shape)}")
+
+
+def pack_exact_hyper_windows(outputscale, noise, mean_constant, lengthscale, B: int) -> torch.Tensor:
+    """Per-window hyper matrix (B, 3 + n_ls), row b = {s2, noise, c, lengthscale...} of window b, for
+    the exact ops' 2-D ``hyper`` (include/gpk.h, the *_perwin_f32 entry points). Each argument is
+    shared (one value in any shape; the lengthscale: 1 or n_ls values) or per-window (leading size
+    B: (B,), (B, 1), (B, 1, n_ls)), so mixed models pack too. A 1-D lengthscale is the shared (n_ls,)
+    vector; a per-window one has at least two dimensions, as GPyTorch's (B, 1, n_ls). Built with
+    expand / cat only: differentiable, a shared entry's gradient sums over the windows through
+    autograd, and no host sync (HIP-graph capturable)."""
+    B = int(B)
+    dev = next((t.device for t in (outputscale, noise, mean_constant, lengthscale)
+                if isinstance(t, torch.Tensor)), None)
+    if isinstance(lengthscale, torch.Tensor):
+        per_window = lengthscale.dim() >= 2 and lengthscale.shape[0] == B
+        n_ls = lengthscale.numel() // max(B, 1) if per_window else lengthscale.numel()
+    else:
+        n_ls = 1
+    parts = [_hyper_piece(outputscale, B, 1, "outputscale", dev), _hyper_piece(noise, B, 1, "noise", dev),
+             _hyper_piece(mean_constant, B, 1, "mean_constant", dev),
+             _hyper_piece(lengthscale, B, n_ls, "lengthscale", dev)]
+    return torch.cat(parts, dim=1).float()
+
+
+def exact_hyper_per_window(outputscale, noise, mean_constant, lengthscale, B: int) -> bool:
+    """Whether any of the hyper-parameters carries a window dimension (leading size B > 1: (B,),
+    (B, 1); the lengthscale (B, 1, n_ls)), i.e. the model is GPyTorch's batch-independent one and
+    packs with ``pack_exact_hyper_windows``. Shapes only: no host sync."""
+    def lead(t, min_dim):
+        return isinstance(t, torch.Tensor) and B > 1 and t.dim() >= min_dim and t.shape[0] == B
+    return lead(outputscale, 1) or lead(noise, 1) or lead(mean_constant, 1) or lead(lengthscale, 2)
+
+
+def _exact_hyper_layout(hyper: torch.Tensor, B: int):
+    """-> (hyper, n_ls, hyp_stride) of an exact op's ``hyper``: 1-D {s2, noise, c, lengthscale...}
+    shared by every window (stride 0), or (B, 3 + n_ls) with one row per window."""
+    if hyper.dim() == 1:
+        return hyper, hyper.shape[-1] - 3, 0
+    if hyper.dim() != 2:
+        raise ValueError(f"hyper must be 1-D (3 + n_ls,) or 2-D (B, 3 + n_ls), got {tuple(hyper.shape)}")
+    if hyper.shape[0] != B:
+        raise ValueError(f"a 2-D hyper must have one row per window: (B, 3 + n_ls) with B = {B}, "
+                         f"got {tuple(hyper.shape)}")
+    hyper = hyper.detach().contiguous().float()
+    return hyper, hyper.shape[-1] - 3, hyper.shape[-1]
+
+
+def _exact_name(base: str, stride: int) -> str:
+    return f"gpk_exact_{base}_perwin_f32" if stride else f"gpk_exact_{base}_f32"
+
+
 @dataclass
 class ExactMLLOut:
     mll: torch.Tensor            # (B,)
@@ -72,6 +134,8 @@ def exact_mll(X: torch.Tensor, y: torch.Tensor, lengthscale, outputscale, mean_c
     X: (B, N, D) float32, y: (B, N) float32 on the same ROCm device. ``lengthscale``
     is a scalar or a length-D vector (ARD). Hyperparameters may be python floats or
     device tensors (no host sync either way). See include/gpk.h::gpk_exact_mll_f32.
+    ``hyper``: the packed vector (3 + n_ls,) shared by every window, or (B, 3 + n_ls) with one row
+    per window (``pack_exact_hyper_windows``; gpk_exact_mll_perwin_f32).
     """
     if X.dim() != 3:
         raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
@@ -84,7 +148,10 @@ def exact_mll(X: torch.Tensor, y: torch.Tensor, lengthscale, outputscale, mean_c
     dev = X.device
     if hyper is None:
         hyper = pack_exact_hyper(outputscale, noise, mean_constant, lengthscale, dev)
-    n_ls = hyper.numel() - 3
+    if hyper.dim() == 1:     # one vector shared by the windows: the per-step launch of a training loop,
+        n_ls, stride = hyper.numel() - 3, 0      # so nothing is added to its host path
+    else:
+        hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     if n_ls not in (1, D):
         raise ValueError(f"lengthscale must have 1 or D={D} entries, got {n_ls}")
     if mll_out is not None and (mll_out.shape != (B,) or mll_out.dtype != torch.float32
@@ -103,11 +170,18 @@ def exact_mll(X: torch.Tensor, y: torch.Tensor, lengthscale, outputscale, mean_c
     need_L = want_L or N > EXACT_REG_MAX_N
     L = (L_out if L_out is not None else torch.empty(B, N, N, device=dev, dtype=torch.float32)) if need_L else None
     z = torch.empty(B, N, device=dev, dtype=torch.float32) if want_z else None
-    rc = _native.lib().gpk_exact_mll_f32(
-        X.data_ptr(), y.data_ptr(), hyper.data_ptr(), n_ls, B, N, D, float(jitter), int(max_tries),
-        L.data_ptr() if L is not None else None, z.data_ptr() if z is not None else None,
-        mll.data_ptr(), info.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_exact_mll_f32")
+    if stride == 0:
+        rc = _native.lib().gpk_exact_mll_f32(
+            X.data_ptr(), y.data_ptr(), hyper.data_ptr(), n_ls, B, N, D, float(jitter), int(max_tries),
+            L.data_ptr() if L is not None else None, z.data_ptr() if z is not None else None,
+            mll.data_ptr(), info.data_ptr(), _stream_ptr(dev))
+    else:
+        rc = _native.lib().gpk_exact_mll_perwin_f32(
+            X.data_ptr(), y.data_ptr(), hyper.data_ptr(), n_ls, stride, B, N, D, float(jitter), int(max_tries),
+            L.data_ptr() if L is not None else None, z.data_ptr() if z is not None else None,
+            mll.data_ptr(), info.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        _native.check(rc, _exact_name("mll", stride))
     return ExactMLLOut(mll, L if want_L else None, z, info)
 
 
@@ -122,7 +196,8 @@ def exact_mll_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: tor
                    gout: torch.Tensor, want_dX: bool = True, want_dy: bool = True) -> ExactMLLGrad:
     """Analytic backward of ``exact_mll`` (one gfx950 kernel launch, see
     include/gpk.h::gpk_exact_mll_grad_f32). ``L`` and ``z`` are the forward's outputs,
-    ``gout`` (B,) the incoming gradient of each window's MLL."""
+    ``gout`` (B,) the incoming gradient of each window's MLL. With a 2-D ``hyper`` (B, 3 + n_ls)
+    row b of ``dhyp`` is the gradient of hyper row b."""
     B, N, D = X.shape
     _require_device(X, L, z, hyper, gout)
     X = X.contiguous().float()
@@ -130,18 +205,19 @@ def exact_mll_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: tor
     z = z.contiguous().float()
     gout = gout.reshape(B).contiguous().float()
     dev = X.device
-    n_ls = hyper.numel() - 3
+    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     lib = _native.lib()
     ws = torch.empty(max(1, lib.gpk_exact_grad_workspace_bytes(B, N) // 4), device=dev,
                      dtype=torch.float32)
     dX = torch.empty(B, N, D, device=dev, dtype=torch.float32) if want_dX else None
     dy = torch.empty(B, N, device=dev, dtype=torch.float32) if want_dy else None
     dhyp = torch.empty(B, 3 + n_ls, device=dev, dtype=torch.float32)
-    rc = lib.gpk_exact_mll_grad_f32(
-        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, B, N, D, gout.data_ptr(),
+    rc = lib.gpk_exact_mll_grad_perwin_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, stride, B, N, D, gout.data_ptr(),
         ws.data_ptr(), dX.data_ptr() if dX is not None else None,
         dy.data_ptr() if dy is not None else None, dhyp.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_exact_mll_grad_f32")
+    if rc != 0:
+        _native.check(rc, _exact_name("mll_grad", stride))
     return ExactMLLGrad(dX, dy, dhyp)
 
 
@@ -155,7 +231,8 @@ def exact_posterior(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: to
                     Xs: torch.Tensor) -> ExactPosterior:
     """Exact-GP posterior at the test inputs ``Xs`` (B, Ns, D) from the training factor
     ``L`` and ``z = L^{-1}(y - c)`` of ``exact_mll`` (one gfx950 kernel launch, see
-    include/gpk.h::gpk_exact_posterior_f32). ``hyper`` is the exact path's device vector."""
+    include/gpk.h::gpk_exact_posterior_f32). ``hyper`` is the exact path's device vector, or
+    (B, 3 + n_ls) with one row per window."""
     if X.dim() != 3 or Xs.dim() != 3:
         raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
     B, N, D = X.shape
@@ -170,12 +247,14 @@ def exact_posterior(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: to
     z = z.detach().contiguous().float()
     Ns = Xs.shape[1]
     dev = X.device
+    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     mean = torch.empty(B, Ns, device=dev, dtype=torch.float32)
     var = torch.empty(B, Ns, device=dev, dtype=torch.float32)
-    rc = _native.lib().gpk_exact_posterior_f32(
-        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), hyper.numel() - 3, Xs.data_ptr(),
+    rc = _native.lib().gpk_exact_posterior_perwin_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, stride, Xs.data_ptr(),
         B, N, Ns, D, mean.data_ptr(), var.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_exact_posterior_f32")
+    if rc != 0:
+        _native.check(rc, _exact_name("posterior", stride))
     return ExactPosterior(mean, var)
 
 
@@ -207,6 +286,7 @@ def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper
     z = z.detach().contiguous().float()
     Ns = Xs.shape[1]
     dev = X.device
+    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     lib = _native.lib()
     nbytes = lib.gpk_exact_posterior_cov_workspace_bytes(B, N, Ns)
     if nbytes == 0 and B > 0 and Ns > 0:
@@ -217,10 +297,11 @@ def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper
     cov = torch.empty(B, Ns, Ns, device=dev, dtype=torch.float32)
     if B == 0 or Ns == 0:
         return (ExactPosteriorCov(mean, var, cov), ws) if return_state else ExactPosteriorCov(mean, var, cov)
-    rc = lib.gpk_exact_posterior_cov_f32(
-        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), hyper.numel() - 3, Xs.data_ptr(),
+    rc = lib.gpk_exact_posterior_cov_perwin_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, stride, Xs.data_ptr(),
         B, N, Ns, D, ws.data_ptr(), mean.data_ptr(), var.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_exact_posterior_cov_f32")
+    if rc != 0:
+        _native.check(rc, _exact_name("posterior_cov", stride))
     return (ExactPosteriorCov(mean, var, cov), ws) if return_state else ExactPosteriorCov(mean, var, cov)
 
 
@@ -250,9 +331,9 @@ def exact_posterior_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hype
     Ns = Xs.shape[1]
     if L.shape != (B, N, N) or z.shape != (B, N):
         raise ValueError("L / z do not match X")
-    n_ls = hyper.numel() - 3
+    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     if n_ls not in (1, D):
-        raise ValueError(f"hyper must have 3 + 1 or 3 + D entries, got {hyper.numel()}")
+        raise ValueError(f"hyper must have 3 + 1 or 3 + D entries per vector, got {hyper.shape[-1]}")
     if gmean is None and gvar is None and gcov is None:
         raise ValueError("at least one of gmean, gvar, gcov must be given")
     for name, g, shape in (("gmean", gmean, (B, Ns)), ("gvar", gvar, (B, Ns)), ("gcov", gcov, (B, Ns, Ns))):
@@ -283,11 +364,12 @@ def exact_posterior_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hype
     state = state.detach().contiguous()
     ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
     ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-    rc = lib.gpk_exact_posterior_grad_f32(
-        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, Xs.data_ptr(), state.data_ptr(),
+    rc = lib.gpk_exact_posterior_grad_perwin_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, stride, Xs.data_ptr(), state.data_ptr(),
         ptr(gmean), ptr(gvar), ptr(gcov), B, N, Ns, D, ws.data_ptr(), ptr(dX), ptr(dy), ptr(dXs),
         dhyp.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_exact_posterior_grad_f32")
+    if rc != 0:
+        _native.check(rc, _exact_name("posterior_grad", stride))
     return ExactPosteriorGrad(dX, dy, dXs, dhyp)
 
 

@@ -41,7 +41,11 @@ def exact_log_prob(X, y, lengthscale, outputscale, constant, noise) -> torch.Ten
     """Per-window exact-GP log marginal likelihood / N (fused HIP kernel forward, analytic
     HIP backward). The hyper vector is packed differentiably, so gpk::exact_mll's
     gradient reaches s2, noise, c and the lengthscale(s)."""
-    hyper = ops.pack_exact_hyper_live(outputscale, noise, constant, lengthscale)
+    if ops.exact_hyper_per_window(outputscale, noise, constant, lengthscale, X.shape[0]):
+        # a batch-independent model: row b of the (B, 3 + n_ls) hyper is window b's own vector
+        hyper = ops.pack_exact_hyper_windows(outputscale, noise, constant, lengthscale, X.shape[0])
+    else:
+        hyper = ops.pack_exact_hyper_live(outputscale, noise, constant, lengthscale)
     need = torch.is_grad_enabled() and any(t.requires_grad for t in (X, y, hyper))
     mll, _, _, info = torch.ops.gpk.exact_mll(X.float(), y.float(), hyper, 1e-6, 3, bool(need))
     ops.check_cholesky_info(info, 1e-6, inputs=(X, y))

@@ -187,6 +187,45 @@ int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z,
                                  float* dX, float* dy, float* dXs, float* dhyp, void* stream);
 
 /*
+ * Per-window hyper-parameters: the five exact entry points above with one hyper vector PER
+ * WINDOW, GPyTorch's batch-independent exact GP (batch_shape = [B] on the mean, the kernel and
+ * the likelihood). Each takes its sibling's arguments plus `hyp_stride` directly after
+ * n_lengthscale, the number of floats between two consecutive windows' hyper vectors:
+ *   hyp_stride == 0 : hyp is one float[3 + n_lengthscale] shared by every window; the call IS the
+ *                     sibling (the siblings are this call with hyp_stride 0), bit for bit
+ *   hyp_stride >= 3 + n_lengthscale : hyp is (B, hyp_stride) row-major and window b reads row b,
+ *                     hyp + b * hyp_stride = {s2, noise, c, lengthscale[n_lengthscale]}; floats of
+ *                     a row past the vector are not read
+ * Window b's kernel matrix, factor, jitter ladder, mll, posterior and gradients then depend on row
+ * b alone. dhyp keeps its dense (B, 3 + n_lengthscale) layout: row b is the gradient with respect
+ * to hyp row b, the same quantity the siblings write, only not meant to be summed over b (a
+ * caller that shares some entries between windows sums those columns itself).
+ * Workspace sizes and every other argument are those of the sibling, and so are the return codes
+ * (argument indices count as in the sibling's list); any other hyp_stride returns minus its own
+ * argument index, -5 from gpk_exact_mll_perwin_f32 and -6 from the other four, before anything is
+ * launched.
+ */
+int gpk_exact_mll_perwin_f32(const float* X, const float* y, const float* hyp, int n_lengthscale,
+                             long long hyp_stride, int B, int N, int D, double jitter, int max_tries,
+                             float* L, float* z, float* mll, int* info, void* stream);
+int gpk_exact_mll_grad_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                  int n_lengthscale, long long hyp_stride, int B, int N, int D,
+                                  const float* gout, void* workspace, float* dX, float* dy, float* dhyp,
+                                  void* stream);
+int gpk_exact_posterior_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                   int n_lengthscale, long long hyp_stride, const float* Xs, int B, int N,
+                                   int Ns, int D, float* mean, float* var, void* stream);
+int gpk_exact_posterior_cov_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                       int n_lengthscale, long long hyp_stride, const float* Xs, int B, int N,
+                                       int Ns, int D, void* workspace, float* mean, float* var, float* cov,
+                                       void* stream);
+int gpk_exact_posterior_grad_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                        int n_lengthscale, long long hyp_stride, const float* Xs,
+                                        const float* state, const float* gmean, const float* gvar,
+                                        const float* gcov, int B, int N, int Ns, int D, void* workspace,
+                                        float* dX, float* dy, float* dXs, float* dhyp, void* stream);
+
+/*
  * Shared inducing-point factorisation of the whitened VariationalStrategy:
  *   A    = K_ZZ + jitter (fp32 add, as K_ZZ.add_jitter), then upcast to fp64
  *   L    = psd_safe_cholesky(A) with the fp64 ladder chol_jitter * 10^t
