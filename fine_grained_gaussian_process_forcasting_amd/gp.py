@@ -712,15 +712,15 @@ class CholeskyVariationalDistribution(nn.Module):
 
     def kl_divergence(self) -> torch.Tensor:
         """KL(q || N(0, I)) = 1/2 (|L_q|_F^2 + |m|^2 - M - sum_k log L_q,kk^2): one gfx950 launch
-        each way for a CUDA fp32 layer (gpk::cholesky_kl for one output, gpk::cholesky_kl_batched
-        for the (O, M) mean of a multi-output layer -> (O,)), the closed form in torch elsewhere."""
+        each way for a CUDA fp32 layer (gpk::cholesky_kl: () for one output, (O,) for the (O, M) mean
+        of a multi-output layer), the closed form in torch elsewhere."""
         m = self.variational_mean
         C = self.chol_variational_covar
         if m.is_cuda and m.dtype == torch.float32 and C.dtype == torch.float32:
             if m.dim() == 1:
                 return torch.ops.gpk.cholesky_kl(m, C).reshape(())
             if m.dim() == 2 and 1 <= m.shape[0] <= 65535 and m.shape[1] <= 16384:
-                return torch.ops.gpk.cholesky_kl_batched(m, C)
+                return torch.ops.gpk.cholesky_kl(m, C)
         return cholesky_kl_closed_form(m, C)
 
 
@@ -781,12 +781,7 @@ def variational_dense_covariance(x, Z, Linv, vstd, outputscale, lengthscale, jit
     ls = lengthscale.reshape(-1)
     s2 = outputscale.reshape(())
     Kxx = rbf_covariance(x, ls, s2)
-    zs = (Z / ls).double()
-    xs = (x / ls).double()
-    d = (zs.pow(2).sum(-1)[:, None] + xs.pow(2).sum(-1).unsqueeze(-2)
-         - 2.0 * zs @ xs.transpose(-1, -2)).clamp_min(0.0)             # (B', M, N)
-    Kzx = s2.double() * torch.exp(-0.5 * d)
-    A = (Linv.double() @ Kzx).to(x.dtype)
+    A = _variational_interp(x, Z, Linv, s2, ls)
     mid = (vstd.reshape(-1).pow(2) - 1.0).to(x.dtype)
     eye = torch.eye(x.shape[-2], dtype=x.dtype, device=x.device)
     return Kxx + jitter * eye + A.transpose(-1, -2) @ (mid[:, None] * A)
@@ -863,12 +858,13 @@ def _variational_chol_cov_grad_on_kernels(x, Z, Linv, vchol, outputscale, length
 
 
 class VariationalStrategy(nn.Module):
-    """Whitened VariationalStrategy for one DeepGP layer (output_dims=None).
+    """Whitened VariationalStrategy for one DeepGP layer: one output (output_dims=None, inducing
+    points (M, D)) or O outputs (inducing points (O, M, D)), mean-field or Cholesky q(u).
 
     __call__(x) with x (..., N, D) returns q(f) as a MultivariateNormal (mean, var)
     computed by gpk_kzz_chol_f64 (ONE fp64 factorisation of the shared K_ZZ, cached across
     the calls of a step / eval batches, ops_autograd.KzzCache) + gpk_variational_f32
-    (column-tiled fp64-MFMA L^{-1} K_ZX, mean, variance).
+    (column-tiled fp64-MFMA L^{-1} K_ZX, mean, variance), or their batched / Cholesky-q(u) forms.
     """
 
     def __init__(self, model, inducing_points: torch.Tensor, variational_distribution,
@@ -908,205 +904,143 @@ class VariationalStrategy(nn.Module):
         return self._variational_distribution.kl_divergence()
 
     def __call__(self, x: torch.Tensor) -> MultivariateNormal:
+        """q(f) at x. One flow for both layer forms and both q(u) kinds:
+
+        1. Normalise to ``lead`` = () -- inducing points (M, D), x (..., N, D) -- or (O,) -- a
+           multi-output layer (output_dims = O, DeepGP.py:24-26): inducing points (O, M, D), q(u) batch
+           (O,), kernel hyper-parameters per output, x (..., O, N, D) as DeepGPLayer.__call__ expands
+           it. That stride-0 expansion (or O == 1) is read in place as one (B', N, D) tensor shared by
+           the outputs: no (O, B', N, D) copy.
+        2. The marginals on the kernels (ops_autograd.variational_predict*): one launch chain each
+           way whatever O is, the K_ZZ factor(s) one KzzCache entry, the per-output dLinv flowing
+           into one K_ZZ adjoint. A mean-field q(u) has no other route (CPU tensors raise). A Cholesky
+           q(u) needs CUDA fp32 inputs and a shape the kernels' queries accept (M <= 256, D <= 64;
+           N <= 256 when a gradient can flow); every other case is variational_chol_predict in torch
+           from the same cached factor, one evaluation per output.
+        3. Reshape back to (..., N) or (..., O, N).
+        4. The dense covariance behind covariance_matrix / rsample, materialised on request
+           (_lazy_covariance)."""
         if not self._initialized:
             self._variational_distribution.initialize_variational_distribution()
             self.variational_params_initialized.fill_(1)
             self._initialized = True
-        if isinstance(self._variational_distribution, CholeskyVariationalDistribution):
-            return self._call_chol(x)
-        if self.inducing_points.dim() == 3:
-            return self._call_batched(x)
-        model = self.model
-        batch = x.shape[:-2]
-        N, D = x.shape[-2:]
-        xf = x.reshape(-1, N, D)
-        kern = model.covar_module
-        key = (self.inducing_points, kern.raw_outputscale, kern.base_kernel.raw_lengthscale)
-        q = self._variational_distribution
-        mean, var, flag, cov = self._predict_one(
-            xf, self.inducing_points, q.variational_mean, q._variational_stddev, kern.outputscale,
-            kern.base_kernel.lengthscale, model.mean_module, self._jitter(x.dtype), self._kzz_cache, key)
-        return MultivariateNormal(mean.reshape(*batch, N), var.reshape(*batch, N), clamp_flag=flag,
-                                  covar_fn=lambda: cov().reshape(*batch, N, N))
-
-    @staticmethod
-    def _predict_one(xf, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter, cache, key):
-        """q(f) of one output on the kernels + a lazy dense covariance for covariance_matrix /
-        rsample (upstream VariationalStrategy.forward's predictive_covar)."""
-        from .ops_autograd import variational_predict
-        mean, var, flag, Linv, hyper = variational_predict(
-            xf, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter, cache=cache,
-            key_tensors=key, return_linv=True, return_hyper=True)
-
-        def cov():
-            if _variational_cov_on_kernels(xf, Z, Linv, vstd, outputscale, lengthscale):
-                return torch.ops.gpk.variational_cov(xf, Linv, Z, vstd, hyper)
-            if _variational_cov_grad_on_kernels(xf, Z, Linv, vstd, outputscale, lengthscale):
-                return torch.ops.gpk.variational_cov_train(xf, Linv, Z, vstd, outputscale.reshape(()),
-                                                           lengthscale.reshape(-1), float(jitter))[0]
-            return variational_dense_covariance(xf, Z, Linv, vstd, outputscale, lengthscale, jitter)
-        return mean, var, flag, cov
-
-    def _call_chol(self, x: torch.Tensor) -> MultivariateNormal:
-        """q(f) with a CholeskyVariationalDistribution. CUDA fp32 inputs and a shape the kernels'
-        queries accept (M <= 256, D <= 64; N <= 256 when a gradient can flow): one output runs
-        ops_autograd.variational_predict_chol (gpk_variational_chol_f32 and its HIP adjoint), a
-        multi-output layer (inducing points (O, M, D), x (..., O, N, D)) runs its O outputs on ONE
-        launch chain each way (ops_autograd.variational_predict_chol_batched,
-        gpk_variational_chol_batched_f32): the O K_ZZ factors are one cache entry, DeepGPLayer's
-        stride-0 expansion of the inputs is read in place (no (O, B, N, D) copy) and the per-output
-        dLinv flow into one batched K_ZZ adjoint. Every other case -- a refused shape, another
-        dtype, CPU tensors -- is variational_chol_predict in torch from the same shared K_ZZ factor
-        (KzzCache), one evaluation per output for a multi-output layer. The dense covariance behind
-        covariance_matrix / rsample is materialised on request: by gpk::variational_chol_cov when no
-        gradient can flow and gpk::variational_chol_cov_train with its HIP adjoint when one can (all
-        outputs of a multi-output layer on one launch chain; dLinv flows into the same Linv as the
-        marginals' and dchol to chol_variational_covar, so the layer still runs one K_ZZ adjoint per
-        step), and by variational_chol_dense_covariance in torch for CPU tensors, other dtypes and
-        shapes the queries refuse."""
-        from .ops_autograd import (_mean_params, _mean_params_batched, variational_predict_chol,
-                                   variational_predict_chol_batched)
+        from . import ops_autograd
         model = self.model
         kern = model.covar_module
         q = self._variational_distribution
+        chol = isinstance(q, CholeskyVariationalDistribution)
         Z = self.inducing_points
         jitter = self._jitter(x.dtype)
         key = (Z, kern.raw_outputscale, kern.base_kernel.raw_lengthscale)
         N, D = x.shape[-2:]
+        M = Z.shape[-2]
         if Z.dim() == 3:
-            O, M, _ = Z.shape
+            O = Z.shape[0]
             if x.dim() < 3 or x.shape[-3] != O:
                 raise RuntimeError(f"a layer with {O} outputs takes inputs (..., {O}, N, D); got {tuple(x.shape)}")
-            batch = x.shape[:-3]
-            s2 = kern.outputscale.reshape(O)
-            ls = kern.base_kernel.lengthscale.reshape(O, -1)
-            vm, vc = q.variational_mean.reshape(O, M), q.chol_variational_covar.reshape(O, M, M)
-            nwin = x.numel() // (O * N * D) if x.numel() > 0 else 0
-            flag = None
-            on_kernels = (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32
-                          and vc.dtype == torch.float32
-                          and ops.variational_chol_batched_supported(O, nwin, N, M, D,
-                                                                     adjoint=torch.is_grad_enabled()))
-            xo = x.movedim(-3, 0).reshape(O, -1, N, D)     # a view of an expanded x: no copy until read
-            if on_kernels:
-                if x.stride(-3) == 0 or O == 1:     # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
-                    xk = x[..., 0, :, :].reshape(-1, N, D)
-                else:
-                    xk = xo
-                mean, var, flag, Linv = variational_predict_chol_batched(
-                    xk, Z, vm, vc, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
-                    return_linv=True)
-                mean = mean.reshape(O, *batch, N).movedim(0, -2)
-                var = var.reshape(O, *batch, N).movedim(0, -2)
+            lead, batch = (O,), x.shape[:-3]
+            if x.stride(-3) == 0 or O == 1:     # DeepGPLayer's expansion: one (B', N, D) tensor for all outputs
+                xk = x[..., 0, :, :].reshape(-1, N, D)
             else:
+                xk = x.movedim(-3, 0).reshape(O, -1, N, D)
+        else:
+            O, lead, batch = None, (), x.shape[:-2]
+            xk = x.reshape(-1, N, D)
+        s2, ls, vm = kern.outputscale, kern.base_kernel.lengthscale, q.variational_mean
+        vq = q.chol_variational_covar if chol else q._variational_stddev
+        if lead:
+            # one view of each parameter for all its consumers. A single output hands the parameters
+            # on as the modules hold them: each consumer takes its own view, so the contributions to
+            # a parameter's gradient (marginals, covariance, KL) are summed in the order they arrive
+            s2, ls, vm = s2.reshape(O), ls.reshape(O, -1), vm.reshape(O, M)
+            vq = vq.reshape(O, M, M) if chol else vq.reshape(O, M)
+
+        on_kernels = True
+        if chol:
+            grad = torch.is_grad_enabled()
+            nwin = xk.shape[-3]
+            on_kernels = (x.is_cuda and x.dtype == torch.float32 and Z.dtype == torch.float32
+                          and vq.dtype == torch.float32
+                          and (ops.variational_chol_batched_supported(O, nwin, N, M, D, adjoint=grad) if lead
+                               else ops.variational_chol_supported(nwin, N, M, D, adjoint=grad)))
+        hyper = None
+        if on_kernels:
+            if chol:
+                predict = (ops_autograd.variational_predict_chol_batched if lead
+                           else ops_autograd.variational_predict_chol)
+                mean, var, flag, Linv = predict(xk, Z, vm, vq, s2, ls, model.mean_module, jitter,
+                                                cache=self._kzz_cache, key_tensors=key, return_linv=True)
+            else:
+                predict = ops_autograd.variational_predict_batched if lead else ops_autograd.variational_predict
+                mean, var, flag, Linv, hyper = predict(xk, Z, vm, vq, s2, ls, model.mean_module, jitter,
+                                                       cache=self._kzz_cache, key_tensors=key,
+                                                       return_linv=True, return_hyper=True)
+        else:
+            flag = None
+            if lead:
                 Linv = self._kzz_cache.factor(Z, s2, ls, jitter, key)
-                w, b0 = _mean_params_batched(model.mean_module, O, D, x.device)
-                outs = [variational_chol_predict(xo[o], Z[o], Linv[o], vm[o], vc[o], s2[o], ls[o],
+                w, b0 = ops_autograd._mean_params_batched(model.mean_module, O, D, x.device)
+                xo = x.movedim(-3, 0).reshape(O, -1, N, D)     # a view of an expanded x
+                outs = [variational_chol_predict(xo[o], Z[o], Linv[o], vm[o], vq[o], s2[o], ls[o],
                                                  w[o] if w.dim() == 2 else w, b0[o] if b0.numel() == O else b0[0],
                                                  jitter) for o in range(O)]
-                mean = torch.stack([m for m, _ in outs]).reshape(O, *batch, N).movedim(0, -2)
-                var = torch.stack([v for _, v in outs]).reshape(O, *batch, N).movedim(0, -2)
-                self._kzz_cache.note_consumers(mean, var)
-                self._kzz_cache.check_pending()
-
-            def cov():
-                # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
-                xc = x[..., 0, :, :].reshape(-1, N, D) if (x.stride(-3) == 0 or O == 1) else xo
-                if _variational_chol_cov_on_kernels(xc, Z, Linv, vc, s2, ls):
-                    from .library import _cov_hyper
-                    hyper = _cov_hyper(xc, Z, s2, ls, float(jitter))
-                    c = torch.ops.gpk.variational_chol_cov(xc, Linv, Z, vc, hyper)     # (O, B', N, N)
-                    return c.reshape(O, *batch, N, N).movedim(0, -3)
-                if _variational_chol_cov_grad_on_kernels(xc, Z, Linv, vc, s2, ls):
-                    c = torch.ops.gpk.variational_chol_cov_train(xc, Linv, Z, vc, s2, ls, float(jitter))[0]
-                    return c.reshape(O, *batch, N, N).movedim(0, -3)
-                return torch.stack([variational_chol_dense_covariance(xo[o], Z[o], Linv[o], vc[o], s2[o], ls[o],
-                                                                      jitter).reshape(*batch, N, N)
-                                    for o in range(O)], dim=-3)
-            return MultivariateNormal(mean.contiguous(), var.contiguous(), clamp_flag=flag, covar_fn=cov)
-
-        batch = x.shape[:-2]
-        M = Z.shape[0]
-        xf = x.reshape(-1, N, D)
-        s2, ls = kern.outputscale, kern.base_kernel.lengthscale
-        vm, vc = q.variational_mean, q.chol_variational_covar
-        grad = torch.is_grad_enabled()
-        on_kernels = (xf.is_cuda and xf.dtype == torch.float32 and Z.dtype == torch.float32
-                      and vc.dtype == torch.float32
-                      and ops.variational_chol_supported(xf.shape[0], N, M, D, adjoint=grad))
-        if on_kernels:
-            mean, var, flag, Linv = variational_predict_chol(
-                xf, Z, vm, vc, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
-                return_linv=True)
-        else:
-            Linv = self._kzz_cache.factor(Z, s2.reshape(()), ls.reshape(-1), jitter, key)
-            w, b0 = _mean_params(model.mean_module, D, x.device)
-            mean, var = variational_chol_predict(xf, Z, Linv, vm, vc, s2, ls, w, b0, jitter)
-            flag = None
+                mean, var = torch.stack([m for m, _ in outs]), torch.stack([v for _, v in outs])
+            else:
+                Linv = self._kzz_cache.factor(Z, s2.reshape(()), ls.reshape(-1), jitter, key)
+                w, b0 = ops_autograd._mean_params(model.mean_module, D, x.device)
+                mean, var = variational_chol_predict(xk, Z, Linv, vm, vq, s2, ls, w, b0, jitter)
             self._kzz_cache.note_consumers(mean, var)
             self._kzz_cache.check_pending()
 
-        def cov():
-            if _variational_chol_cov_on_kernels(xf, Z, Linv, vc, s2, ls):
-                from .library import _cov_hyper
-                hyper = _cov_hyper(xf, Z, s2.reshape(()), ls.reshape(-1), float(jitter))
-                return torch.ops.gpk.variational_chol_cov(xf, Linv, Z, vc, hyper).reshape(*batch, N, N)
-            if _variational_chol_cov_grad_on_kernels(xf, Z, Linv, vc, s2, ls):
-                return torch.ops.gpk.variational_chol_cov_train(
-                    xf, Linv, Z, vc, s2.reshape(()), ls.reshape(-1), float(jitter))[0].reshape(*batch, N, N)
-            return variational_chol_dense_covariance(xf, Z, Linv, vc, s2, ls, jitter).reshape(*batch, N, N)
-        return MultivariateNormal(mean.reshape(*batch, N), var.reshape(*batch, N), clamp_flag=flag,
-                                  covar_fn=cov)
-
-    def _call_batched(self, x: torch.Tensor) -> MultivariateNormal:
-        """Multi-output layer (output_dims = O, DeepGP.py:24-26): inducing points (O, M, D), q(u)
-        batch (O,), kernel hyper-parameters per output; x (..., O, N, D) as DeepGPLayer.__call__
-        expands it. The O outputs are independent GPs on ONE launch chain each way
-        (ops_autograd.variational_predict_batched): the O K_ZZ factors are one cache entry, the
-        expanded inputs are read in place by every output (no (O, B, N, D) copy), and the
-        per-output dLinv flow into one batched K_ZZ adjoint. Returns the batch (..., O) of
-        per-output q(f); the covariance is materialised on request, by the kernels
-        (all outputs on one launch chain: gpk::variational_cov when no gradient can flow,
-        gpk::variational_cov_train with its HIP adjoint when one can; dLinv then flows into the
-        same Linv as the marginals' and the layer still runs one K_ZZ adjoint per step), and as
-        dense torch arithmetic from Linv[o] for CPU tensors, other dtypes and refused shapes."""
-        from .ops_autograd import variational_predict_batched
-        Z = self.inducing_points
-        O, M, D = Z.shape
-        if x.dim() < 3 or x.shape[-3] != O:
-            raise RuntimeError(f"a layer with {O} outputs takes inputs (..., {O}, N, D); got {tuple(x.shape)}")
-        batch = x.shape[:-3]
-        N = x.shape[-2]
-        model = self.model
-        kern = model.covar_module
-        q = self._variational_distribution
-        key = (Z, kern.raw_outputscale, kern.base_kernel.raw_lengthscale)
-        s2 = kern.outputscale.reshape(O)
-        ls = kern.base_kernel.lengthscale.reshape(O, -1)
-        vm = q.variational_mean.reshape(O, M)
-        vs = q._variational_stddev.reshape(O, M)
-        jitter = self._jitter(x.dtype)
-        if x.stride(-3) == 0 or O == 1:     # DeepGPLayer's expansion: one (B, N, D) tensor for all outputs
-            xk = x[..., 0, :, :].reshape(-1, N, D)
+        if lead:
+            mean = mean.reshape(O, *batch, N).movedim(0, -2).contiguous()
+            var = var.reshape(O, *batch, N).movedim(0, -2).contiguous()
         else:
-            xk = x.movedim(-3, 0).reshape(O, -1, N, D)
-        mean, var, flag, Linv, hyper = variational_predict_batched(
-            xk, Z, vm, vs, s2, ls, model.mean_module, jitter, cache=self._kzz_cache, key_tensors=key,
-            return_linv=True, return_hyper=True)
+            mean, var = mean.reshape(*batch, N), var.reshape(*batch, N)
+        cov = self._lazy_covariance(chol, x, xk, Z, Linv, vq, s2, ls, jitter, hyper, batch)
+        return MultivariateNormal(mean, var, clamp_flag=flag, covar_fn=cov)
+
+    @staticmethod
+    def _lazy_covariance(chol, x, xk, Z, Linv, vq, s2, ls, jitter, hyper, batch):
+        """The closure behind covariance_matrix / rsample (upstream VariationalStrategy.forward's
+        predictive_covar) for a mean-field (``vq`` the stddevs) or Cholesky (``chol``: ``vq`` the factor)
+        q(u): on the kernels when no gradient can flow (gpk::variational_cov / _chol_cov) and, with
+        their HIP adjoint, when one can (gpk::variational_cov_train / _chol_cov_train; dLinv then
+        flows into the same Linv as the marginals' and the layer still runs one K_ZZ adjoint per step),
+        all outputs of a multi-output layer on one launch chain; as dense torch arithmetic from
+        Linv[o] for CPU tensors, other dtypes and shapes the queries refuse."""
+        N, D = x.shape[-2:]
+        lead = tuple(Z.shape[:-2])
+
+        def op_hypers():     # the ops take s2 (), ls (D,); a multi-output layer's are (O,), (O, D) already
+            return (s2, ls) if lead else (s2.reshape(()), ls.reshape(-1))
 
         def cov():
-            if _variational_cov_on_kernels(xk, Z, Linv, vs, s2, ls):
-                c = torch.ops.gpk.variational_cov(xk, Linv, Z, vs, hyper)       # (O, B', N, N)
-                return c.reshape(O, *batch, N, N).movedim(0, -3)
-            if _variational_cov_grad_on_kernels(xk, Z, Linv, vs, s2, ls):
-                c = torch.ops.gpk.variational_cov_train(xk, Linv, Z, vs, s2, ls, float(jitter))[0]
-                return c.reshape(O, *batch, N, N).movedim(0, -3)
-            xo =xk.expand(O, *xk.shape) if xk.dim() == 3 else xk
-            return torch.stack([variational_dense_covariance(xo[o], Z[o], Linv[o], vs[o], s2[o], ls[o], jitter)
-                                .reshape(*batch, N, N) for o in range(O)], dim=-3)
-        return MultivariateNormal(mean.reshape(O, *batch, N).movedim(0, -2).contiguous(),
-                                  var.reshape(O, *batch, N).movedim(0, -2).contiguous(), clamp_flag=flag,
-                                  covar_fn=cov)
+            if chol:
+                on_kernels, grad_on_kernels = _variational_chol_cov_on_kernels, _variational_chol_cov_grad_on_kernels
+                cov_op, train_op = torch.ops.gpk.variational_chol_cov, torch.ops.gpk.variational_chol_cov_train
+                dense = variational_chol_dense_covariance
+            else:
+                on_kernels, grad_on_kernels = _variational_cov_on_kernels, _variational_cov_grad_on_kernels
+                cov_op, train_op = torch.ops.gpk.variational_cov, torch.ops.gpk.variational_cov_train
+                dense = variational_dense_covariance
+            if on_kernels(xk, Z, Linv, vq, s2, ls):
+                h = hyper
+                if h is None:     # the Cholesky forward's vector is not kept: packed on request
+                    from .library import _cov_hyper
+                    h = _cov_hyper(xk, Z, *op_hypers(), float(jitter))
+                c = cov_op(xk, Linv, Z, vq, h)                         # (*lead, B', N, N)
+            elif grad_on_kernels(xk, Z, Linv, vq, s2, ls):
+                c = train_op(xk, Linv, Z, vq, *op_hypers(), float(jitter))[0]
+            elif not lead:
+                c = dense(xk, Z, Linv, vq, s2, ls, jitter)
+            else:
+                xo = x.movedim(-3, 0).reshape(lead[0], -1, N, D)
+                return torch.stack([dense(xo[o], Z[o], Linv[o], vq[o], s2[o], ls[o], jitter).reshape(*batch, N, N)
+                                    for o in range(lead[0])], dim=-3)
+            c = c.reshape(*lead, *batch, N, N)
+            return c.movedim(0, -3) if lead else c
+        return cov
 
 
 # ---------------------------------------------------------------------------

@@ -18,17 +18,16 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter) -> (mean, var, flags, hyper)
                                                                                [autograd]
   gpk::variational_adj(x, Linv, Z, vmean, vstd, hyper, gmean, gvar) -> (dX, dLinv, dZ, dpar)
-  gpk::kzz_factor_batched / gpk::variational_fwd_batched / gpk::variational_adj_batched
-      the three ops above for the O output GPs of a multi-output layer (leading O on every
-      array, the inputs shared or per output), one launch chain for all outputs    [autograd]
+      (the three above also for the O output GPs of a multi-output layer, Z (O, M, D): a leading O
+      on every array, the inputs shared or per output, one launch chain for all outputs)
   gpk::variational_chol_fwd(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save)
       -> (mean, var, flags, hyper, saved): q(u) = N(vmean, tril(vchol) tril(vchol)^T)    [autograd]
   gpk::variational_chol_adj(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved)
       -> (dX, dLinv, dZ, dpar, dchol)
   gpk::cholesky_kl(m, chol) -> kl (1,)                                        [autograd]
-  gpk::variational_chol_fwd_batched / gpk::variational_chol_adj_batched / gpk::cholesky_kl_batched /
-  gpk::cholesky_kl_grad_batched
-      the three above for the O outputs of a multi-output layer, one launch chain each way [autograd]
+  gpk::cholesky_kl_grad(m, chol, gkl) -> (dm, dchol)
+      (the four above also for the O outputs of a multi-output layer, one launch chain each way:
+      Z (O, M, D); m (O, M), chol (O, M, M) -> kl (O,))
   gpk::gauss_ell(y, mean, var, noise) -> ell (R,)                             [autograd]
   gpk::meanfield_kl(m, s) -> kl (1,)                                          [autograd]
   gpk::variational_elbo(y, mean, var, noise, m, s, kl_scale, min_var) -> (elbo (R,), flag)
@@ -216,25 +215,66 @@ def _exact_backward(ctx, gmll, _gL, _gz, _ginfo):
 exact_mll.register_autograd(_exact_backward, setup_context=_exact_setup)
 
 # ---------------------------------------------------------------------------
+# The variational ops below take both forms of a layer: Z (M, D) is one GP; Z (O, M, D) the O output
+# GPs of a multi-output layer (output_dims = O) on ONE launch chain, every per-output array with a
+# leading O (``lead`` = Z.shape[:-2]) and the inputs x (B, N, D) shared by the outputs or
+# (O, B, N, D). The op bodies dispatch on Z.dim() to the single or the ``_batched`` name of ops.py;
+# the kernels return per-dimension, per-output gradients, which the helpers below fold.
+# ---------------------------------------------------------------------------
+
+
+def _fold_x(dX, x, Z):
+    """dX (O, B, N, D) per output -> the gradient of inputs (B, N, D) shared by the outputs."""
+    return dX.sum(0) if Z.dim() == 3 and x.dim() == 3 else dX
+
+
+def _fold_ls(dls, ls, Z):
+    """dls (..., D) per dimension -> the gradient of ``ls``: summed over D for a lengthscale shared
+    by the dimensions (one value; one per output for Z (O, M, D))."""
+    if Z.dim() == 3:
+        return dls.sum(-1).reshape(ls.shape) if ls.numel() == Z.shape[0] else dls.reshape(ls.shape)
+    return dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
+
+
+def _fold_mean(dw, db0, w, b0, Z):
+    """dw (..., D), db0 (...) -> the gradients of the mean's w and b0: summed over O for a mean
+    shared by the outputs (w (D,), b0 one value)."""
+    if Z.dim() == 3:
+        dw = dw.sum(0) if w.numel() == Z.shape[-1] else dw
+        db0 = db0.sum() if b0.numel() == 1 else db0
+    return dw.reshape(w.shape), db0.reshape(b0.shape)
+
+
+# ---------------------------------------------------------------------------
 # shared K_ZZ factor (gpk_kzz_chol_f64) + its M x M adjoint (ops.kzz_backward)
 # ---------------------------------------------------------------------------
+
+
+def _kzz_hyper_batched(Z, s2, ls):
+    O, _, D = Z.shape
+    return torch.cat([s2.detach().reshape(O, 1).float(), ls.detach().reshape(O, -1).expand(O, D).float()], dim=1)
 
 
 @torch.library.custom_op("gpk::kzz_factor", mutates_args=(), device_types="cuda")
 def kzz_factor(Z: Tensor, s2: Tensor, ls: Tensor, jitter: float, chol_jitter: float,
                max_tries: int) -> Tuple[Tensor, Tensor, Tensor]:
-    D = Z.shape[-1]
-    lsv = ls.detach().reshape(-1).expand(D).contiguous().float()
-    kz = ops.kzz_cholesky(Z.detach(), None, None, jitter=jitter, chol_jitter=chol_jitter,
-                          max_tries=max_tries, hyper=torch.cat([s2.detach().reshape(1).float(), lsv]))
+    """Z (M, D), s2 (), ls (D,) or (1,) -> (Linv, L (M, M) float64, info (1,)); Z (O, M, D), s2 (O,),
+    ls (O, D) or (O, 1) -> (Linv, L (O, M, M), info (O,))."""
+    if Z.dim() == 3:
+        kz = ops.kzz_cholesky_batched(Z.detach(), _kzz_hyper_batched(Z, s2, ls), jitter=jitter,
+                                      chol_jitter=chol_jitter, max_tries=max_tries)
+    else:
+        lsv = ls.detach().reshape(-1).expand(Z.shape[-1]).contiguous().float()
+        kz = ops.kzz_cholesky(Z.detach(), None, None, jitter=jitter, chol_jitter=chol_jitter,
+                              max_tries=max_tries, hyper=torch.cat([s2.detach().reshape(1).float(), lsv]))
     return kz.Linv, kz.L, kz.info
 
 
 @kzz_factor.register_fake
 def _(Z, s2, ls, jitter, chol_jitter, max_tries):
-    M = Z.shape[0]
-    return (Z.new_empty(M, M, dtype=torch.float64), Z.new_empty(M, M, dtype=torch.float64),
-            Z.new_empty(1, dtype=torch.int32))
+    lead, M = Z.shape[:-2], Z.shape[-2]
+    return (Z.new_empty(*lead, M, M, dtype=torch.float64), Z.new_empty(*lead, M, M, dtype=torch.float64),
+            Z.new_empty(tuple(lead) or (1,), dtype=torch.int32))
 
 
 def _kzz_setup(ctx, inputs, output):
@@ -245,19 +285,24 @@ def _kzz_setup(ctx, inputs, output):
 
 
 def _kzz_backward(ctx, dLinv, _dL, _dinfo):
+    """The dLinv of every call that shared the factor(s) -> one K_ZZ adjoint."""
     Z, s2, ls, L, Linv = ctx.saved_tensors
     if dLinv is None:
         return None, None, None, None, None, None
-    dZ, ds2, dls = ops.kzz_backward(dLinv, L, Linv, Z, s2, ls)
-    dls_out = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
-    return (dZ.to(Z.dtype), ds2.reshape(s2.shape).to(s2.dtype), dls_out.to(ls.dtype),
+    if Z.dim() == 3:
+        dZ, dhyp = ops.kzz_backward_batched(dLinv, L, Linv, Z, _kzz_hyper_batched(Z, s2, ls))
+        ds2, dls = dhyp[:, 0], dhyp[:, 1:]
+    else:
+        dZ, ds2, dls = ops.kzz_backward(dLinv, L, Linv, Z, s2, ls)
+    return (dZ.to(Z.dtype), ds2.reshape(s2.shape).to(s2.dtype), _fold_ls(dls, ls, Z).to(ls.dtype),
             None, None, None)
 
 
 kzz_factor.register_autograd(_kzz_backward, setup_context=_kzz_setup)
 
 # ---------------------------------------------------------------------------
-# variational predictive distribution (gpk_variational_f32 / gpk_variational_adjoint_f32)
+# variational predictive distribution (gpk_variational_f32 / gpk_variational_adjoint_f32 and
+# gpk_variational_batched_f32 / gpk_variational_adjoint_batched_f32)
 # ---------------------------------------------------------------------------
 
 
@@ -265,127 +310,6 @@ def _var_hyper(x, s2, ls, w, b0, jitter):
     D = x.shape[-1]
     lsv = ls.detach().reshape(-1).expand(D).contiguous().float()
     return ops.pack_variational_hyper(s2.detach(), 1.0, jitter, b0.detach(), w.detach(), lsv, D, x.device)
-
-
-def _saved_numel(x, Z, save):
-    if not save:
-        return 0
-    B, N, D = x.shape
-    return _native.lib().gpk_variational_saved_bytes(B, N, Z.shape[0], D) // 4
-
-
-@torch.library.custom_op("gpk::variational_fwd", mutates_args=(), device_types="cuda")
-def variational_fwd(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, s2: Tensor,
-                    ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
-                    save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """-> (mean, var, clamp flags, packed hyper vector, saved state). The hyper vector is
-    returned so the backward reuses it (one pack per GP call, not one per direction).
-    ``save`` (a gradient will be needed): the forward keeps A = Linv K_ZX and the clamp mask
-    for the saved-state adjoint where it serves the shape (M > 64; gpk_variational_train_f32),
-    else the state is empty and the adjoint recomputes."""
-    hyper = _var_hyper(x, s2, ls, w, b0, jitter)
-    out = ops.variational_forward(x, Z, Linv, vmean, vstd, hyper=hyper, save=save)
-    saved = out.saved if out.saved is not None else x.new_empty(0)
-    return out.mean, out.var, out.flags, hyper, saved
-
-
-@variational_fwd.register_fake
-def _(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter, save=False):
-    B, N, D = x.shape
-    return (x.new_empty(B, N), x.new_empty(B, N), x.new_empty(1, dtype=torch.int32),
-            x.new_empty(4 + 2 * D), x.new_empty(_saved_numel(x, Z, save)))
-
-
-@torch.library.custom_op("gpk::variational_adj", mutates_args=(), device_types="cuda")
-def variational_adj(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, hyper: Tensor,
-                    gmean: Tensor, gvar: Tensor, saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """-> (dX, dLinv, dZ (K_ZX part), dpar = [dvmean (M), dvstd (M), ds2, dls (D), dw (D), db0]).
-    ``saved``: the forward's state (empty: recompute the forward inside the adjoint)."""
-    adj = ops.variational_adjoint(x, Z, Linv, vmean, vstd, hyper, gmean, gvar,
-                                  saved=saved if saved.numel() > 0 else None)
-    return adj.dX, adj.dLinv, adj.dZ, adj.dpar
-
-
-@variational_adj.register_fake
-def _(x, Linv, Z, vmean, vstd, hyper, gmean, gvar, saved):
-    M, D = Z.shape
-    return (torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z),
-            x.new_empty(2 * M + 2 * D + 2))
-
-
-def _var_setup(ctx, inputs, output):
-    x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter = inputs[:10]
-    ctx.save_for_backward(x, Linv, Z, vmean, vstd, s2, ls, w, b0, output[3], output[4])
-    ctx.mark_non_differentiable(output[2], output[3], output[4])
-
-
-def _var_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
-    x, Linv, Z, vmean, vstd, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
-    B, N, D = x.shape
-    M = Z.shape[0]
-    if gmean is None:
-        gmean = x.new_zeros(B, N)
-    if gvar is None:
-        gvar = x.new_zeros(B, N)
-    dX, dLinv, dZ, dpar = torch.ops.gpk.variational_adj(x, Linv, Z, vmean, vstd, hyper,
-                                                        gmean.contiguous(), gvar.contiguous(), saved)
-    dls = dpar[2 * M + 1:2 * M + 1 + D]
-    dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
-    return (dX, dLinv, dZ, dpar[:M].reshape(vmean.shape), dpar[M:2 * M].reshape(vstd.shape),
-            dpar[2 * M].reshape(s2.shape), dls, dpar[2 * M + 1 + D:2 * M + 1 + 2 * D].reshape(w.shape),
-            dpar[2 * M + 1 + 2 * D].reshape(b0.shape), None, None)
-
-
-variational_fwd.register_autograd(_var_backward, setup_context=_var_setup)
-
-# ---------------------------------------------------------------------------
-# multi-output layers (output_dims = O): the same chain with an output dimension, ONE launch
-# of every kernel for all outputs (gpk_kzz_chol_f64_batched / gpk_variational_batched_f32 /
-# gpk_variational_adjoint_batched_f32 / gpk_kzz_backward_f64_batched)
-# ---------------------------------------------------------------------------
-
-
-def _kzz_hyper_batched(Z, s2, ls):
-    O, _, D = Z.shape
-    return torch.cat([s2.detach().reshape(O, 1).float(), ls.detach().reshape(O, -1).expand(O, D).float()], dim=1)
-
-
-@torch.library.custom_op("gpk::kzz_factor_batched", mutates_args=(), device_types="cuda")
-def kzz_factor_batched(Z: Tensor, s2: Tensor, ls: Tensor, jitter: float, chol_jitter: float,
-                       max_tries: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """Z (O, M, D), s2 (O,), ls (O, D) or (O, 1) -> (Linv, L (O, M, M) float64, info (O,))."""
-    kz = ops.kzz_cholesky_batched(Z.detach(), _kzz_hyper_batched(Z, s2, ls), jitter=jitter,
-                                  chol_jitter=chol_jitter, max_tries=max_tries)
-    return kz.Linv, kz.L, kz.info
-
-
-@kzz_factor_batched.register_fake
-def _(Z, s2, ls, jitter, chol_jitter, max_tries):
-    O, M, _ = Z.shape
-    return (Z.new_empty(O, M, M, dtype=torch.float64), Z.new_empty(O, M, M, dtype=torch.float64),
-            Z.new_empty(O, dtype=torch.int32))
-
-
-def _kzzb_setup(ctx, inputs, output):
-    Z, s2, ls = inputs[:3]
-    Linv, L, info = output
-    ctx.save_for_backward(Z, s2, ls, L, Linv)
-    ctx.mark_non_differentiable(L, info)
-
-
-def _kzzb_backward(ctx, dLinv, _dL, _dinfo):
-    """The per-output dLinv of every call that shared the factors -> one batched K_ZZ adjoint."""
-    Z, s2, ls, L, Linv = ctx.saved_tensors
-    if dLinv is None:
-        return None, None, None, None, None, None
-    O, _, D = Z.shape
-    dZ, dhyp = ops.kzz_backward_batched(dLinv, L, Linv, Z, _kzz_hyper_batched(Z, s2, ls))
-    dls = dhyp[:, 1:]
-    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
-    return (dZ.to(Z.dtype), dhyp[:, 0].reshape(s2.shape).to(s2.dtype), dls.to(ls.dtype), None, None, None)
-
-
-kzz_factor_batched.register_autograd(_kzzb_backward, setup_context=_kzzb_setup)
 
 
 def _var_hyper_batched(x, O, s2, ls, w, b0, jitter):
@@ -398,82 +322,96 @@ def _var_hyper_batched(x, O, s2, ls, w, b0, jitter):
                       ls.detach().reshape(O, -1).expand(O, D).float()], dim=1)
 
 
-def _saved_numel_batched(x, Z, save):
+def _pack_hyper(x, Z, s2, ls, w, b0, jitter):
+    """The packed hyper vector of the variational kernels: (4 + 2D,), or (O, 4 + 2D) for Z (O, M, D).
+    Two packers: one output goes through ops.pack_variational_hyper and its cached constants (one
+    cat kernel per call)."""
+    if Z.dim() == 3:
+        return _var_hyper_batched(x, Z.shape[0], s2, ls, w, b0, jitter)
+    return _var_hyper(x, s2, ls, w, b0, jitter)
+
+
+def _saved_numel(x, Z, save):
     if not save:
         return 0
     B, N, D = x.shape[-3:]
-    return Z.shape[0] * (_native.lib().gpk_variational_saved_bytes(B, N, Z.shape[1], D) // 4)
+    O = Z.shape[0] if Z.dim() == 3 else 1
+    return O * (_native.lib().gpk_variational_saved_bytes(B, N, Z.shape[-2], D) // 4)
 
 
-@torch.library.custom_op("gpk::variational_fwd_batched", mutates_args=(), device_types="cuda")
-def variational_fwd_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, s2: Tensor,
-                            ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
-                            save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """x (B, N, D) shared by the O outputs, or (O, B, N, D); Linv (O, M, M), Z (O, M, D),
-    vmean / vstd (O, M), s2 (O,), ls (O, D) or (O, 1); the mean per output (w (O, D), b0 (O,))
-    or shared (w (D,), b0 one value) -> (mean, var (O, B, N), clamp flags (1,), packed hyper
-    (O, 4 + 2D), saved state), as gpk::variational_fwd."""
-    hyper = _var_hyper_batched(x, Z.shape[0], s2, ls, w, b0, jitter)
-    out = ops.variational_forward_batched(x, Z, Linv, vmean, vstd, hyper, save=save)
+@torch.library.custom_op("gpk::variational_fwd", mutates_args=(), device_types="cuda")
+def variational_fwd(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, s2: Tensor,
+                    ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
+                    save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (mean, var, clamp flags, packed hyper vector, saved state). The hyper vector is
+    returned so the backward reuses it (one pack per GP call, not one per direction).
+    ``save`` (a gradient will be needed): the forward keeps A = Linv K_ZX and the clamp mask
+    for the saved-state adjoint where it serves the shape (M > 64; gpk_variational_train_f32),
+    else the state is empty and the adjoint recomputes.
+    Z (O, M, D): Linv (O, M, M), vmean / vstd (O, M), s2 (O,), ls (O, D) or (O, 1); the mean per
+    output (w (O, D), b0 (O,)) or shared (w (D,), b0 one value) -> mean, var (O, B, N), clamp flags
+    (1,), packed hyper (O, 4 + 2D)."""
+    hyper = _pack_hyper(x, Z, s2, ls, w, b0, jitter)
+    if Z.dim() == 3:
+        out = ops.variational_forward_batched(x, Z, Linv, vmean, vstd, hyper, save=save)
+    else:
+        out = ops.variational_forward(x, Z, Linv, vmean, vstd, hyper=hyper, save=save)
     saved = out.saved if out.saved is not None else x.new_empty(0)
     return out.mean, out.var, out.flags, hyper, saved
 
 
-@variational_fwd_batched.register_fake
+@variational_fwd.register_fake
 def _(x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter, save=False):
     B, N, D = x.shape[-3:]
-    O = Z.shape[0]
-    return (x.new_empty(O, B, N), x.new_empty(O, B, N), x.new_empty(1, dtype=torch.int32),
-            x.new_empty(O, 4 + 2 * D), x.new_empty(_saved_numel_batched(x, Z, save)))
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, B, N), x.new_empty(*lead, B, N), x.new_empty(1, dtype=torch.int32),
+            x.new_empty(*lead, 4 + 2 * D), x.new_empty(_saved_numel(x, Z, save)))
 
 
-@torch.library.custom_op("gpk::variational_adj_batched", mutates_args=(), device_types="cuda")
-def variational_adj_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, hyper: Tensor,
-                            gmean: Tensor, gvar: Tensor,
-                            saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """-> (dX (O, B, N, D) per output, dLinv (O, M, M), dZ (O, M, D), dpar (O, 2M + 2D + 2))."""
-    adj = ops.variational_adjoint_batched(x, Z, Linv, vmean, vstd, hyper, gmean, gvar,
-                                          saved=saved if saved.numel() > 0 else None)
+@torch.library.custom_op("gpk::variational_adj", mutates_args=(), device_types="cuda")
+def variational_adj(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vstd: Tensor, hyper: Tensor,
+                    gmean: Tensor, gvar: Tensor, saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """-> (dX, dLinv, dZ (K_ZX part), dpar = [dvmean (M), dvstd (M), ds2, dls (D), dw (D), db0]).
+    ``saved``: the forward's state (empty: recompute the forward inside the adjoint).
+    Z (O, M, D): dX (O, B, N, D) per output, dLinv (O, M, M), dZ (O, M, D), dpar (O, 2M + 2D + 2)."""
+    adjoint = ops.variational_adjoint_batched if Z.dim() == 3 else ops.variational_adjoint
+    adj = adjoint(x, Z, Linv, vmean, vstd, hyper, gmean, gvar, saved=saved if saved.numel() > 0 else None)
     return adj.dX, adj.dLinv, adj.dZ, adj.dpar
 
 
-@variational_adj_batched.register_fake
+@variational_adj.register_fake
 def _(x, Linv, Z, vmean, vstd, hyper, gmean, gvar, saved):
-    O, M, D = Z.shape
-    B, N = x.shape[-3], x.shape[-2]
-    return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
-            x.new_empty(O, 2 * M + 2 * D + 2))
+    M, D = Z.shape[-2:]
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, *x.shape[-3:]), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(*lead, 2 * M + 2 * D + 2))
 
 
-def _varb_setup(ctx, inputs, output):
+def _var_setup(ctx, inputs, output):
     x, Linv, Z, vmean, vstd, s2, ls, w, b0, jitter = inputs[:10]
     ctx.save_for_backward(x, Linv, Z, vmean, vstd, s2, ls, w, b0, output[3], output[4])
     ctx.mark_non_differentiable(output[2], output[3], output[4])
 
 
-def _varb_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
+def _var_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
     x, Linv, Z, vmean, vstd, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
-    O, M, D = Z.shape
-    B, N = x.shape[-3], x.shape[-2]
+    M, D = Z.shape[-2:]
+    shape = Z.shape[:-2] + x.shape[-3:-1]
     if gmean is None:
-        gmean = x.new_zeros(O, B, N)
+        gmean = x.new_zeros(shape)
     if gvar is None:
-        gvar = x.new_zeros(O, B, N)
-    dX, dLinv, dZ, dpar = torch.ops.gpk.variational_adj_batched(x, Linv, Z, vmean, vstd, hyper,
-                                                                gmean.contiguous(), gvar.contiguous(), saved)
-    if x.dim() == 3:
-        dX = dX.sum(0)                      # inputs shared by the outputs
-    dls = dpar[:, 2 * M + 1:2 * M + 1 + D]
-    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
-    dw = dpar[:, 2 * M + 1 + D:2 * M + 1 + 2 * D]
-    dw = dw.sum(0).reshape(w.shape) if w.numel() == D else dw.reshape(w.shape)   # a mean shared by the outputs
-    db0 = dpar[:, 2 * M + 1 + 2 * D]
-    db0 = db0.sum().reshape(b0.shape) if b0.numel() == 1 else db0.reshape(b0.shape)
-    return (dX, dLinv, dZ, dpar[:, :M].reshape(vmean.shape), dpar[:, M:2 * M].reshape(vstd.shape),
-            dpar[:, 2 * M].reshape(s2.shape), dls, dw, db0, None, None)
+        gvar = x.new_zeros(shape)
+    dX, dLinv, dZ, dpar = torch.ops.gpk.variational_adj(x, Linv, Z, vmean, vstd, hyper,
+                                                        gmean.contiguous(), gvar.contiguous(), saved)
+    dX = _fold_x(dX, x, Z)
+    dls = _fold_ls(dpar[..., 2 * M + 1:2 * M + 1 + D], ls, Z)
+    dw, db0 = _fold_mean(dpar[..., 2 * M + 1 + D:2 * M + 1 + 2 * D], dpar[..., 2 * M + 1 + 2 * D], w, b0, Z)
+    return (dX, dLinv, dZ, dpar[..., :M].reshape(vmean.shape), dpar[..., M:2 * M].reshape(vstd.shape),
+            dpar[..., 2 * M].reshape(s2.shape), dls, dw, db0, None, None)
 
 
-variational_fwd_batched.register_autograd(_varb_backward, setup_context=_varb_setup)
+variational_fwd.register_autograd(_var_backward, setup_context=_var_setup)
+
 
 # ---------------------------------------------------------------------------
 # ELBO terms (gpk_gauss_ell_f32 / gpk_meanfield_kl_f32)
@@ -614,9 +552,7 @@ def variational_cov(x: Tensor, Linv: Tensor, Z: Tensor, vstd: Tensor, hyper: Ten
 @variational_cov.register_fake
 def _(x, Linv, Z, vstd, hyper):
     B, N = x.shape[-3], x.shape[-2]
-    if Z.dim() == 3:
-        return x.new_empty(Z.shape[0], B, N, N)
-    return x.new_empty(B, N, N)
+    return x.new_empty(*Z.shape[:-2], B, N, N)
 
 
 # The differentiable covariance (gpk_variational_cov_f32 keeping its workspace as the saved state,
@@ -626,11 +562,7 @@ def _(x, Linv, Z, vstd, hyper):
 def _cov_hyper(x, Z, s2, ls, jitter):
     """The packed hyper vector gpk_variational_cov_f32 reads (s2, jitter and the lengthscales; the
     mean's entries are not read and stay 0): (4 + 2D,), or (O, 4 + 2D) for Z (O, M, D)."""
-    D = x.shape[-1]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        return _var_hyper_batched(x, O, s2, ls, x.new_zeros(D), x.new_zeros(1), jitter)
-    return _var_hyper(x, s2, ls, x.new_zeros(D), x.new_zeros(()), jitter)
+    return _pack_hyper(x, Z, s2, ls, x.new_zeros(x.shape[-1]), x.new_zeros(1), jitter)
 
 
 @torch.library.custom_op("gpk::variational_cov_train", mutates_args=(), device_types="cuda")
@@ -659,10 +591,8 @@ def _cov_state_numel(x, Z):
 @variational_cov_train.register_fake
 def _(x, Linv, Z, vstd, s2, ls, jitter):
     B, N, D = x.shape[-3:]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        return x.new_empty(O, B, N, N), x.new_empty(O, 4 + 2 * D), x.new_empty(_cov_state_numel(x, Z))
-    return x.new_empty(B, N, N), x.new_empty(4 + 2 * D), x.new_empty(_cov_state_numel(x, Z))
+    lead = Z.shape[:-2]
+    return x.new_empty(*lead, B, N, N), x.new_empty(*lead, 4 + 2 * D), x.new_empty(_cov_state_numel(x, Z))
 
 
 @torch.library.custom_op("gpk::variational_cov_grad", mutates_args=(), device_types="cuda")
@@ -677,13 +607,10 @@ def variational_cov_grad(x: Tensor, Linv: Tensor, Z: Tensor, vstd: Tensor, hyper
 
 @variational_cov_grad.register_fake
 def _(x, Linv, Z, vstd, hyper, state, gcov):
-    B, N, D = x.shape[-3:]
-    M = Z.shape[-2]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
-                x.new_empty(O, M + 1 + D))
-    return torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(M + 1 + D)
+    M, D = Z.shape[-2:]
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, *x.shape[-3:]), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(*lead, M + 1 + D))
 
 
 def _covt_setup(ctx, inputs, output):
@@ -698,15 +625,8 @@ def _covt_backward(ctx, gcov, _ghyper, _gstate):
     M, D = Z.shape[-2:]
     dX, dLinv, dZ, dpar = torch.ops.gpk.variational_cov_grad(x, Linv, Z, vstd, hyper, state,
                                                              gcov.contiguous())
-    dls = dpar[..., M + 1:]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        if x.dim() == 3:
-            dX = dX.sum(0)                      # inputs shared by the outputs
-        dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
-    else:
-        dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
-    return (dX, dLinv, dZ, dpar[..., :M].reshape(vstd.shape), dpar[..., M].reshape(s2.shape), dls, None)
+    return (_fold_x(dX, x, Z), dLinv, dZ, dpar[..., :M].reshape(vstd.shape), dpar[..., M].reshape(s2.shape),
+            _fold_ls(dpar[..., M + 1:], ls, Z), None)
 
 
 variational_cov_train.register_autograd(_covt_backward, setup_context=_covt_setup)
@@ -726,9 +646,7 @@ def variational_chol_cov(x: Tensor, Linv: Tensor, Z: Tensor, vchol: Tensor, hype
 @variational_chol_cov.register_fake
 def _(x, Linv, Z, vchol, hyper):
     B, N = x.shape[-3], x.shape[-2]
-    if Z.dim() == 3:
-        return x.new_empty(Z.shape[0], B, N, N)
-    return x.new_empty(B, N, N)
+    return x.new_empty(*Z.shape[:-2], B, N, N)
 
 
 @torch.library.custom_op("gpk::variational_chol_cov_train", mutates_args=(), device_types="cuda")
@@ -754,10 +672,9 @@ def _chol_cov_state_numel(x, Z):
 @variational_chol_cov_train.register_fake
 def _(x, Linv, Z, vchol, s2, ls, jitter):
     B, N, D = x.shape[-3:]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        return x.new_empty(O, B, N, N), x.new_empty(O, 4 + 2 * D), x.new_empty(_chol_cov_state_numel(x, Z))
-    return x.new_empty(B, N, N), x.new_empty(4 + 2 * D), x.new_empty(_chol_cov_state_numel(x, Z))
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, B, N, N), x.new_empty(*lead, 4 + 2 * D),
+            x.new_empty(_chol_cov_state_numel(x, Z)))
 
 
 @torch.library.custom_op("gpk::variational_chol_cov_grad", mutates_args=(), device_types="cuda")
@@ -770,13 +687,9 @@ def variational_chol_cov_grad(x: Tensor, Linv: Tensor, Z: Tensor, vchol: Tensor,
 
 @variational_chol_cov_grad.register_fake
 def _(x, Linv, Z, vchol, hyper, state, gcov):
-    B, N, D = x.shape[-3:]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(O, 1 + D),
-                torch.empty_like(vchol))
-    return (torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(1 + D),
-            torch.empty_like(vchol))
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, *x.shape[-3:]), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(*lead, 1 + Z.shape[-1]), torch.empty_like(vchol))
 
 
 def _ccovt_setup(ctx, inputs, output):
@@ -790,15 +703,8 @@ def _ccovt_backward(ctx, gcov, _ghyper, _gstate):
     x, Linv, Z, vchol, s2, ls, hyper, state = ctx.saved_tensors
     dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_cov_grad(x, Linv, Z, vchol, hyper, state,
                                                                          gcov.contiguous())
-    dls = dpar[..., 1:]
-    if Z.dim() == 3:
-        O = Z.shape[0]
-        if x.dim() == 3:
-            dX = dX.sum(0)                      # inputs shared by the outputs
-        dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
-    else:
-        dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
-    return (dX, dLinv, dZ, dchol.reshape(vchol.shape), dpar[..., 0].reshape(s2.shape), dls, None)
+    return (_fold_x(dX, x, Z), dLinv, dZ, dchol.reshape(vchol.shape), dpar[..., 0].reshape(s2.shape),
+            _fold_ls(dpar[..., 1:], ls, Z), None)
 
 
 variational_chol_cov_train.register_autograd(_ccovt_backward, setup_context=_ccovt_setup)
@@ -917,15 +823,19 @@ mvn_root.register_autograd(_mvn_root_backward, setup_context=_mvn_root_setup)
 
 # ---------------------------------------------------------------------------
 # Cholesky (full-covariance) q(u): gpk_variational_chol_f32 / gpk_variational_chol_adjoint_f32 /
-# gpk_cholesky_kl_f32 (upstream CholeskyVariationalDistribution inside VariationalStrategy)
+# gpk_cholesky_kl_f32 and their batched forms (upstream CholeskyVariationalDistribution inside
+# VariationalStrategy); Z (M, D) or (O, M, D) as above, m (M,) or (O, M) for the KL
 # ---------------------------------------------------------------------------
 
 
 def _chol_saved_numel(x, Z, save):
-    if not save or x.shape[0] < 1:
+    B, N, D = x.shape[-3:]
+    if not save or B < 1:
         return 0
-    B, N, D = x.shape
-    return _native.lib().gpk_variational_chol_saved_bytes(B, N, Z.shape[0], D) // 4
+    lib = _native.lib()
+    if Z.dim() == 3:
+        return lib.gpk_variational_chol_batched_saved_bytes(Z.shape[0], B, N, Z.shape[1], D) // 4
+    return lib.gpk_variational_chol_saved_bytes(B, N, Z.shape[0], D) // 4
 
 
 @torch.library.custom_op("gpk::variational_chol_fwd", mutates_args=(), device_types="cuda")
@@ -934,18 +844,21 @@ def variational_chol_fwd(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vcho
                          save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (mean, var, clamp flags, packed hyper vector, saved state): gpk::variational_fwd with
     q(u) = N(vmean, tril(vchol) tril(vchol)^T). ``save`` (a gradient will be needed): the forward
-    keeps A = Linv K_ZX and the clamp mask, which the adjoint reads; else the state is empty."""
-    hyper = _var_hyper(x, s2, ls, w, b0, jitter)
-    out = ops.variational_chol_forward(x, Z, Linv, vmean, vchol, hyper, save=save)
+    keeps A = Linv K_ZX and the clamp mask, which the adjoint reads; else the state is empty.
+    Z (O, M, D): vmean (O, M), vchol (O, M, M), the other arguments as gpk::variational_fwd."""
+    hyper = _pack_hyper(x, Z, s2, ls, w, b0, jitter)
+    forward = ops.variational_chol_forward_batched if Z.dim() == 3 else ops.variational_chol_forward
+    out = forward(x, Z, Linv, vmean, vchol, hyper, save=save)
     saved = out.saved if out.saved is not None else x.new_empty(0)
     return out.mean, out.var, out.flags, hyper, saved
 
 
 @variational_chol_fwd.register_fake
 def _(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save=False):
-    B, N, D = x.shape
-    return (x.new_empty(B, N), x.new_empty(B, N), x.new_empty(1, dtype=torch.int32),
-            x.new_empty(4 + 2 * D), x.new_empty(_chol_saved_numel(x, Z, save)))
+    B, N, D = x.shape[-3:]
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, B, N), x.new_empty(*lead, B, N), x.new_empty(1, dtype=torch.int32),
+            x.new_empty(*lead, 4 + 2 * D), x.new_empty(_chol_saved_numel(x, Z, save)))
 
 
 @torch.library.custom_op("gpk::variational_chol_adj", mutates_args=(), device_types="cuda")
@@ -953,15 +866,18 @@ def variational_chol_adj(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vcho
                          gmean: Tensor, gvar: Tensor,
                          saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
     """-> (dX, dLinv, dZ (K_ZX part), dpar = [dvmean (M), ds2, dls (D), dw (D), db0], dchol (M, M)
-    lower) from the forward's ``saved`` state."""
-    return ops.variational_chol_adjoint(x, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+    lower) from the forward's ``saved`` state. Z (O, M, D): dX (O, B, N, D) per output and every
+    other array with a leading O."""
+    adjoint = ops.variational_chol_adjoint_batched if Z.dim() == 3 else ops.variational_chol_adjoint
+    return adjoint(x, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
 
 
 @variational_chol_adj.register_fake
 def _(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved):
-    M, D = Z.shape
-    return (torch.empty_like(x), torch.empty_like(Linv), torch.empty_like(Z), x.new_empty(M + 2 * D + 2),
-            x.new_empty(M, M))
+    M, D = Z.shape[-2:]
+    lead = Z.shape[:-2]
+    return (x.new_empty(*lead, *x.shape[-3:]), torch.empty_like(Linv), torch.empty_like(Z),
+            x.new_empty(*lead, M + 2 * D + 2), x.new_empty(*lead, M, M))
 
 
 def _vchol_setup(ctx, inputs, output):
@@ -972,25 +888,26 @@ def _vchol_setup(ctx, inputs, output):
 
 def _vchol_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
     x, Linv, Z, vmean, vchol, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
-    B, N, D = x.shape
-    M = Z.shape[0]
+    M, D = Z.shape[-2:]
+    lead = Z.shape[:-2]
+    B, N = x.shape[-3], x.shape[-2]
     if saved.numel() == 0 and B > 0:
         raise RuntimeError("gpk::variational_chol_fwd was called with save=False; no backward")
     if gmean is None:
-        gmean = x.new_zeros(B, N)
+        gmean = x.new_zeros(*lead, B, N)
     if gvar is None:
-        gvar = x.new_zeros(B, N)
+        gvar = x.new_zeros(*lead, B, N)
     if B == 0:
-        dX, dLinv, dZ = torch.zeros_like(x), torch.zeros_like(Linv), torch.zeros_like(Z)
-        dpar, dchol = x.new_zeros(M + 2 * D + 2), x.new_zeros(M, M)
+        dX, dLinv, dZ = x.new_zeros(*lead, B, N, D), torch.zeros_like(Linv), torch.zeros_like(Z)
+        dpar, dchol = x.new_zeros(*lead, M + 2 * D + 2), x.new_zeros(*lead, M, M)
     else:
         dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_adj(
             x, Linv, Z, vmean, vchol, hyper, gmean.contiguous(), gvar.contiguous(), saved)
-    dls = dpar[M + 1:M + 1 + D]
-    dls = dls.sum().reshape(ls.shape) if ls.numel() == 1 else dls.reshape(ls.shape)
-    return (dX, dLinv, dZ, dpar[:M].reshape(vmean.shape), dchol.reshape(vchol.shape), dpar[M].reshape(s2.shape),
-            dls, dpar[M + 1 + D:M + 1 + 2 * D].reshape(w.shape), dpar[M + 1 + 2 * D].reshape(b0.shape),
-            None, None)
+    dX = _fold_x(dX, x, Z)
+    dls = _fold_ls(dpar[..., M + 1:M + 1 + D], ls, Z)
+    dw, db0 = _fold_mean(dpar[..., M + 1 + D:M + 1 + 2 * D], dpar[..., M + 1 + 2 * D], w, b0, Z)
+    return (dX, dLinv, dZ, dpar[..., :M].reshape(vmean.shape), dchol.reshape(vchol.shape),
+            dpar[..., M].reshape(s2.shape), dls, dw, db0, None, None)
 
 
 variational_chol_fwd.register_autograd(_vchol_backward, setup_context=_vchol_setup)
@@ -998,17 +915,22 @@ variational_chol_fwd.register_autograd(_vchol_backward, setup_context=_vchol_set
 
 @torch.library.custom_op("gpk::cholesky_kl", mutates_args=(), device_types="cuda")
 def cholesky_kl(m: Tensor, chol: Tensor) -> Tensor:
-    """(1,) KL(N(m, L L^T) || N(0, I)), L = tril(chol), of the whitened Cholesky q(u)."""
+    """(1,) KL(N(m, L L^T) || N(0, I)), L = tril(chol), of the whitened Cholesky q(u); m (O, M),
+    chol (O, M, M): the (O,) KLs of the outputs in one launch."""
+    if m.dim() == 2:
+        return ops.cholesky_kl_batched(m, chol)
     return ops.cholesky_kl(m.contiguous().float(), chol.contiguous().float())
 
 
 @cholesky_kl.register_fake
 def _(m, chol):
-    return m.new_empty(1)
+    return m.new_empty(m.shape[0] if m.dim() == 2 else 1)
 
 
 @torch.library.custom_op("gpk::cholesky_kl_grad", mutates_args=(), device_types="cuda")
 def cholesky_kl_grad(m: Tensor, chol: Tensor, gkl: Tensor) -> Tuple[Tensor, Tensor]:
+    if m.dim() == 2:
+        return ops.cholesky_kl_grad_batched(m, chol, gkl)
     return ops.cholesky_kl_grad(m.contiguous().float(), chol.contiguous().float(),
                                 gkl.reshape(1).contiguous().float())
 
@@ -1024,131 +946,8 @@ def _ckl_setup(ctx, inputs, output):
 
 def _ckl_backward(ctx, gkl):
     m, chol = ctx.saved_tensors
-    dm, dchol = torch.ops.gpk.cholesky_kl_grad(m, chol, gkl)
+    dm, dchol = torch.ops.gpk.cholesky_kl_grad(m, chol, gkl.contiguous())
     return dm, dchol
 
 
 cholesky_kl.register_autograd(_ckl_backward, setup_context=_ckl_setup)
-
-# ---------------------------------------------------------------------------
-# Cholesky q(u) of a multi-output layer: gpk_variational_chol_batched_f32 /
-# gpk_variational_chol_adjoint_batched_f32 / gpk_cholesky_kl_batched_f32 (O outputs, every launch once)
-# ---------------------------------------------------------------------------
-
-
-def _chol_saved_numel_batched(x, Z, save):
-    B, N, D = x.shape[-3:]
-    if not save or B < 1:
-        return 0
-    O, M, _ = Z.shape
-    return _native.lib().gpk_variational_chol_batched_saved_bytes(O, B, N, M, D) // 4
-
-
-@torch.library.custom_op("gpk::variational_chol_fwd_batched", mutates_args=(), device_types="cuda")
-def variational_chol_fwd_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor, s2: Tensor,
-                                 ls: Tensor, w: Tensor, b0: Tensor, jitter: float,
-                                 save: bool = False) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """gpk::variational_chol_fwd for O outputs: x (B, N, D) shared by the outputs, or (O, B, N, D);
-    Linv (O, M, M), Z (O, M, D), vmean (O, M), vchol (O, M, M), s2 (O,), ls (O, D) or (O, 1); the
-    mean per output (w (O, D), b0 (O,)) or shared (w (D,), b0 one value) -> (mean, var (O, B, N),
-    clamp flags (1,), packed hyper (O, 4 + 2D), saved state)."""
-    hyper = _var_hyper_batched(x, Z.shape[0], s2, ls, w, b0, jitter)
-    out = ops.variational_chol_forward_batched(x, Z, Linv, vmean, vchol, hyper, save=save)
-    saved = out.saved if out.saved is not None else x.new_empty(0)
-    return out.mean, out.var, out.flags, hyper, saved
-
-
-@variational_chol_fwd_batched.register_fake
-def _(x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter, save=False):
-    B, N, D = x.shape[-3:]
-    O = Z.shape[0]
-    return (x.new_empty(O, B, N), x.new_empty(O, B, N), x.new_empty(1, dtype=torch.int32),
-            x.new_empty(O, 4 + 2 * D), x.new_empty(_chol_saved_numel_batched(x, Z, save)))
-
-
-@torch.library.custom_op("gpk::variational_chol_adj_batched", mutates_args=(), device_types="cuda")
-def variational_chol_adj_batched(x: Tensor, Linv: Tensor, Z: Tensor, vmean: Tensor, vchol: Tensor,
-                                 hyper: Tensor, gmean: Tensor, gvar: Tensor,
-                                 saved: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    """-> (dX (O, B, N, D) per output, dLinv (O, M, M), dZ (O, M, D), dpar (O, M + 2D + 2) =
-    [dvmean (M), ds2, dls (D), dw (D), db0] per output, dchol (O, M, M) lower)."""
-    return ops.variational_chol_adjoint_batched(x, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
-
-
-@variational_chol_adj_batched.register_fake
-def _(x, Linv, Z, vmean, vchol, hyper, gmean, gvar, saved):
-    O, M, D = Z.shape
-    B, N = x.shape[-3], x.shape[-2]
-    return (x.new_empty(O, B, N, D), torch.empty_like(Linv), torch.empty_like(Z),
-            x.new_empty(O, M + 2 * D + 2), x.new_empty(O, M, M))
-
-
-def _vcholb_setup(ctx, inputs, output):
-    x, Linv, Z, vmean, vchol, s2, ls, w, b0, jitter = inputs[:10]
-    ctx.save_for_backward(x, Linv, Z, vmean, vchol, s2, ls, w, b0, output[3], output[4])
-    ctx.mark_non_differentiable(output[2], output[3], output[4])
-
-
-def _vcholb_backward(ctx, gmean, gvar, _gflags, _ghyper, _gsaved):
-    x, Linv, Z, vmean, vchol, s2, ls, w, b0, hyper, saved = ctx.saved_tensors
-    O, M, D = Z.shape
-    B, N = x.shape[-3], x.shape[-2]
-    if saved.numel() == 0 and B > 0:
-        raise RuntimeError("gpk::variational_chol_fwd_batched was called with save=False; no backward")
-    if gmean is None:
-        gmean = x.new_zeros(O, B, N)
-    if gvar is None:
-        gvar = x.new_zeros(O, B, N)
-    if B == 0:
-        dX, dLinv, dZ = x.new_zeros(O, B, N, D), torch.zeros_like(Linv), torch.zeros_like(Z)
-        dpar, dchol = x.new_zeros(O, M + 2 * D + 2), x.new_zeros(O, M, M)
-    else:
-        dX, dLinv, dZ, dpar, dchol = torch.ops.gpk.variational_chol_adj_batched(
-            x, Linv, Z, vmean, vchol, hyper, gmean.contiguous(), gvar.contiguous(), saved)
-    if x.dim() == 3:
-        dX = dX.sum(0)                      # inputs shared by the outputs
-    dls = dpar[:, M + 1:M + 1 + D]
-    dls = dls.sum(-1).reshape(ls.shape) if ls.numel() == O else dls.reshape(ls.shape)
-    dw = dpar[:, M + 1 + D:M + 1 + 2 * D]
-    dw = dw.sum(0).reshape(w.shape) if w.numel() == D else dw.reshape(w.shape)   # a mean shared by the outputs
-    db0 = dpar[:, M + 1 + 2 * D]
-    db0 = db0.sum().reshape(b0.shape) if b0.numel() == 1 else db0.reshape(b0.shape)
-    return (dX, dLinv, dZ, dpar[:, :M].reshape(vmean.shape), dchol.reshape(vchol.shape),
-            dpar[:, M].reshape(s2.shape), dls, dw, db0, None, None)
-
-
-variational_chol_fwd_batched.register_autograd(_vcholb_backward, setup_context=_vcholb_setup)
-
-
-@torch.library.custom_op("gpk::cholesky_kl_batched", mutates_args=(), device_types="cuda")
-def cholesky_kl_batched(m: Tensor, chol: Tensor) -> Tensor:
-    """(O,) KL(N(m_o, L_o L_o^T) || N(0, I)), L_o = tril(chol_o): m (O, M), chol (O, M, M)."""
-    return ops.cholesky_kl_batched(m, chol)
-
-
-@cholesky_kl_batched.register_fake
-def _(m, chol):
-    return m.new_empty(m.shape[0])
-
-
-@torch.library.custom_op("gpk::cholesky_kl_grad_batched", mutates_args=(), device_types="cuda")
-def cholesky_kl_grad_batched(m: Tensor, chol: Tensor, gkl: Tensor) -> Tuple[Tensor, Tensor]:
-    return ops.cholesky_kl_grad_batched(m, chol, gkl)
-
-
-@cholesky_kl_grad_batched.register_fake
-def _(m, chol, gkl):
-    return torch.empty_like(m), torch.empty_like(chol)
-
-
-def _cklb_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs)
-
-
-def _cklb_backward(ctx, gkl):
-    m, chol = ctx.saved_tensors
-    dm, dchol = torch.ops.gpk.cholesky_kl_grad_batched(m, chol, gkl.contiguous())
-    return dm, dchol
-
-
-cholesky_kl_batched.register_autograd(_cklb_backward, setup_context=_cklb_setup)

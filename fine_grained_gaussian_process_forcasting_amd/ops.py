@@ -557,47 +557,202 @@ LOG_2PI = math.log(2 * math.pi)
 
 
 # ---------------------------------------------------------------------------
-# Variational (DeepGP) path
+# Variational (DeepGP) path. One body per operation: the rank of Z selects the form -- Z (M, D) is
+# one GP, Z (O, M, D) the O independent output GPs of a multi-output layer in one launch of every
+# kernel (include/gpk.h::gpk_*_batched; ToyDeepGPHiddenLayer(output_dims=O), DeepGP.py:24-31) --
+# ``lead`` = () or (O,) is the leading shape of every per-output array, and the C entry point is
+# chosen at one place in the body. The public single and ``_batched`` names check their rank and
+# call the body.
 # ---------------------------------------------------------------------------
+def _ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def _single_output(Z: torch.Tensor) -> None:
+    if Z.dim() != 2:
+        raise ValueError(f"Z must be (M, D), got {tuple(Z.shape)}")
+
+
+def _multi_output(Z: torch.Tensor) -> None:
+    if Z.dim() != 3:
+        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
+
+
+def _batched_x(X: torch.Tensor, O: int):
+    """(contiguous float X, shared flag): X (B, N, D) is read by every output; an (O, B, N, D)
+    tensor whose output dimension is an expansion (stride 0) too, without a copy."""
+    if X.dim() == 3:
+        return X.detach().contiguous().float(), True
+    if X.dim() != 4 or X.shape[0] != O:
+        raise ValueError(f"X must be (B, N, D) or (O, B, N, D) with O = {O}, got {tuple(X.shape)}")
+    if O > 1 and X.stride(0) == 0:
+        return X[0].detach().contiguous().float(), True
+    return X.detach().contiguous().float(), False
+
+
+def _var_args(X, Z, Linv, hyper, cast_linv: bool = False):
+    """Checked, contiguous arguments of a variational op -> (X, shared, Z, Linv, hyper, lead, O or
+    None, B, N, M, D). ``hyper`` is pack_variational_hyper's vector, one row per output. The
+    forwards require a float64 Linv; the adjoints (``cast_linv``) convert it."""
+    if Z.dim() == 3:
+        O, M, D = Z.shape
+        X, shared = _batched_x(X, O)
+        lead = (O,)
+    elif Z.dim() == 2:
+        O, (M, D) = None, Z.shape
+        if X.dim() != 3:
+            raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
+        X, shared, lead = X.detach().contiguous().float(), True, ()
+    else:
+        raise ValueError(f"Z must be (M, D) or (O, M, D), got {tuple(Z.shape)}")
+    B, N = X.shape[-3], X.shape[-2]
+    if X.shape[-1] != D:
+        raise ValueError(f"Z must be (..., M, {X.shape[-1]}), got {tuple(Z.shape)}")
+    if cast_linv:
+        Linv = Linv.double()
+    if tuple(Linv.shape) != lead + (M, M) or Linv.dtype != torch.float64:
+        raise ValueError(f"Linv must be {lead + (M, M)} float64 from kzz_cholesky")
+    if tuple(hyper.shape) != lead + (4 + 2 * D,):
+        raise ValueError(f"hyper must be {lead + (4 + 2 * D,)}, got {tuple(hyper.shape)}")
+    return (X, shared, Z.detach().contiguous().float(), Linv.detach().contiguous(),
+            hyper.detach().contiguous().float(), lead, O, B, N, M, D)
+
+
+def _per_output(t: torch.Tensor, *shape) -> torch.Tensor:
+    """A q(u) parameter or an incoming gradient as a contiguous float32 array of ``shape``."""
+    return t.detach().reshape(shape).contiguous().float()
+
+
+def _vchol_arg(vchol: torch.Tensor, lead, M: int) -> torch.Tensor:
+    if tuple(vchol.shape) != lead + (M, M):
+        raise ValueError(f"chol_variational_covar must be {lead + (M, M)}, got {tuple(vchol.shape)}")
+    return vchol.detach().contiguous().float()
+
+
+def _abi(X, shared, O, *sizes):
+    """The two places where a batched entry point's argument list differs from the single one: the
+    input pointer is followed by its shared flag, and the sizes are preceded by O."""
+    if O is None:
+        return (X.data_ptr(),), sizes
+    return (X.data_ptr(), int(shared)), (O,) + sizes
+
+
 @dataclass
 class KzzFactor:
-    L: torch.Tensor      # (M, M) float64 lower Cholesky factor of K_ZZ + jitter
-    Linv: torch.Tensor   # (M, M) float64 L^{-1}
-    info: torch.Tensor   # (1,) int32
+    L: torch.Tensor      # (M, M) float64 lower Cholesky factor of K_ZZ + jitter; (O, M, M) for O outputs
+    Linv: torch.Tensor   # (M, M) float64 L^{-1}; (O, M, M)
+    info: torch.Tensor   # (1,) int32; (O,)
+
+
+def _kzz_cholesky(Z, hyper, jitter, chol_jitter, max_tries) -> KzzFactor:
+    """Z (float32, contiguous) and hyper = {outputscale, lengthscale[D]} per output, both checked."""
+    lead, (M, D) = tuple(Z.shape[:-2]), Z.shape[-2:]
+    dev = Z.device
+    L = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    Linv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    info = torch.empty(lead or (1,), device=dev, dtype=torch.int32)
+    name = "gpk_kzz_chol_f64_batched" if lead else "gpk_kzz_chol_f64"
+    rc = getattr(_native.lib(), name)(Z.data_ptr(), hyper.data_ptr(), *lead, M, D, float(jitter),
+                                      float(chol_jitter), int(max_tries), L.data_ptr(), Linv.data_ptr(),
+                                      info.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return KzzFactor(L, Linv, info)
 
 
 def kzz_cholesky(Z: torch.Tensor, outputscale, lengthscale, jitter: float = 1e-4,
                  chol_jitter: float = 1e-8, max_tries: int = 3,
                  hyper: Optional[torch.Tensor] = None) -> KzzFactor:
     """Shared inducing-point factorisation (include/gpk.h::gpk_kzz_chol_f64)."""
-    if Z.dim() != 2:
-        raise ValueError(f"Z must be (M, D), got {tuple(Z.shape)}")
+    _single_output(Z)
     _require_device(Z)
     Z = Z.detach().contiguous().float()
-    M, D = Z.shape
-    dev = Z.device
+    D = Z.shape[1]
     if hyper is None:
-        hyper = torch.cat([_scalar_tensor(outputscale, dev)[:1],
-                           _scalar_tensor(lengthscale, dev).expand(D) if _scalar_tensor(lengthscale, dev).numel() == 1
-                           else _scalar_tensor(lengthscale, dev)]).contiguous()
+        ls = _scalar_tensor(lengthscale, Z.device)
+        hyper = torch.cat([_scalar_tensor(outputscale, Z.device)[:1],
+                           ls.expand(D) if ls.numel() == 1 else ls]).contiguous()
     if hyper.numel() != 1 + D:
         raise ValueError(f"kzz hyper must hold 1 + D = {1 + D} values, got {hyper.numel()}")
-    L = torch.empty(M, M, device=dev, dtype=torch.float64)
-    Linv = torch.empty(M, M, device=dev, dtype=torch.float64)
-    info = torch.empty(1, device=dev, dtype=torch.int32)
-    rc = _native.lib().gpk_kzz_chol_f64(Z.data_ptr(), hyper.data_ptr(), M, D, float(jitter),
-                                        float(chol_jitter), int(max_tries), L.data_ptr(),
-                                        Linv.data_ptr(), info.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_kzz_chol_f64")
-    return KzzFactor(L, Linv, info)
+    return _kzz_cholesky(Z, hyper, jitter, chol_jitter, max_tries)
+
+
+def kzz_cholesky_batched(Z: torch.Tensor, hyper: torch.Tensor, jitter: float = 1e-4,
+                         chol_jitter: float = 1e-8, max_tries: int = 3) -> KzzFactor:
+    """The K_ZZ factors of O outputs (include/gpk.h::gpk_kzz_chol_f64_batched): Z (O, M, D),
+    hyper (O, 1 + D) = {outputscale, lengthscale[D]} per output -> L, Linv (O, M, M) float64
+    and info (O,), bit-identical to O ``kzz_cholesky`` calls."""
+    _multi_output(Z)
+    _require_device(Z, hyper)
+    O, _, D = Z.shape
+    if tuple(hyper.shape) != (O, 1 + D):
+        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
+    return _kzz_cholesky(Z.detach().contiguous().float(), hyper.detach().contiguous().float(), jitter,
+                         chol_jitter, max_tries)
+
+
+def _kzz_backward(dLinv, L, Linv, Z, hyper):
+    """-> (dZ (..., M, D) float, dhyp (..., 1 + D) = {ds2, dlengthscale[D]} per output)."""
+    _require_device(dLinv, L, Linv, Z, hyper)
+    lead, (M, D) = tuple(Z.shape[:-2]), Z.shape[-2:]
+    dev = Z.device
+    lib = _native.lib()
+    if lead:
+        name = "gpk_kzz_backward_f64_batched"
+        nbytes = lib.gpk_kzz_backward_batched_workspace_bytes(*lead, M, D)
+        if nbytes == 0:
+            raise ValueError(f"unsupported K_ZZ shape O={lead[0]} M={M} D={D}")
+    else:
+        name = "gpk_kzz_backward_f64"
+        nbytes = lib.gpk_kzz_backward_workspace_bytes(M, D)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
+    dhyp = torch.empty(*lead, 1 + D, device=dev, dtype=torch.float32)
+    rc = getattr(lib, name)(
+        dLinv.detach().contiguous().double().data_ptr(), L.detach().contiguous().double().data_ptr(),
+        Linv.detach().contiguous().double().data_ptr(), Z.detach().contiguous().float().data_ptr(),
+        hyper.detach().contiguous().float().data_ptr(), *lead, M, D, ws.data_ptr(), dZ.data_ptr(),
+        dhyp.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return dZ, dhyp
+
+
+def kzz_backward(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: torch.Tensor,
+                 outputscale: torch.Tensor, lengthscale: torch.Tensor):
+    """Back-propagate dObjective/dLinv (lower, fp64) through Linv = chol(K_ZZ + jitter)^{-1}
+    to (dZ, d outputscale, d lengthscale): once per optimizer step for all GP calls that
+    shared the factor (include/gpk.h::gpk_kzz_backward_f64: five fp64-MFMA tile GEMMs
+    Lbar = -tril(Linv^T G Linv^T), S = Linv^T Phi(L^T Lbar) Linv, then the RBF adjoint over
+    K_ZZ with Kbar = (S + S^T)/2). Returns (dZ (M, D) float, ds2 (), dls (D,)) -- dls per
+    dimension even for a shared lengthscale (the caller sums)."""
+    _single_output(Z)
+    D = Z.shape[1]
+    ls = lengthscale.detach().reshape(-1).float()
+    hyper = torch.cat([outputscale.detach().reshape(1).float(), ls.expand(D) if ls.numel() == 1 else ls])
+    dZ, dhyp = _kzz_backward(dLinv, L, Linv, Z, hyper)
+    return dZ, dhyp[0], dhyp[1:]
+
+
+def kzz_backward_batched(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: torch.Tensor,
+                         hyper: torch.Tensor):
+    """``kzz_backward`` for O outputs, every launch once (gpk_kzz_backward_f64_batched):
+    dLinv, L, Linv (O, M, M) float64, Z (O, M, D), hyper (O, 1 + D) -> (dZ (O, M, D),
+    dhyp (O, 1 + D) = {ds2, dlengthscale[D]} per output)."""
+    _multi_output(Z)
+    O, M, D = Z.shape
+    for name, t in (("dLinv", dLinv), ("L", L), ("Linv", Linv)):
+        if tuple(t.shape) != (O, M, M):
+            raise ValueError(f"{name} must be (O, M, M) = {(O, M, M)}, got {tuple(t.shape)}")
+    if tuple(hyper.shape) != (O, 1 + D):
+        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
+    return _kzz_backward(dLinv, L, Linv, Z, hyper)
 
 
 @dataclass
 class VariationalOut:
-    mean: torch.Tensor           # (B, N)
-    var: torch.Tensor            # (B, N) clamped at 1e-6
-    ell: Optional[torch.Tensor]  # (B,) sum over N of the expected log likelihood
-    flags: Optional[torch.Tensor]  # (1,) int32: bit 0 = the variance clamp fired
+    mean: torch.Tensor           # (B, N); (O, B, N) for O outputs
+    var: torch.Tensor            # as mean, clamped at 1e-6
+    ell: Optional[torch.Tensor]  # (B,) sum over N of the expected log likelihood (one output, with y)
+    flags: Optional[torch.Tensor]  # (1,) int32: bit 0 = the variance clamp fired (one word for all outputs)
     saved: Optional[torch.Tensor] = None  # training state for variational_adjoint (M > 64), or None
 
 
@@ -634,6 +789,42 @@ def pack_variational_hyper(outputscale, noise, jitter, bias, weights, lengthscal
                       w, ls]).contiguous()
 
 
+def _variational_forward(X, Z, Linv, vmean, vstd, hyper, y, want_flags, save) -> VariationalOut:
+    _require_device(X, Z, Linv, vmean, vstd, hyper)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
+    dev = X.device
+    vmean = _per_output(vmean, *lead, M)
+    vstd = _per_output(vstd, *lead, M)
+    if y is not None:
+        if y.shape != (B, N):
+            raise ValueError(f"y must be (B, N) = {(B, N)}, got {tuple(y.shape)}")
+        _require_device(y)
+        y = y.detach().contiguous().float()
+    mean = torch.empty(*lead, B, N, device=dev, dtype=torch.float32)
+    var = torch.empty(*lead, B, N, device=dev, dtype=torch.float32)
+    ell = torch.empty(B, device=dev, dtype=torch.float32) if y is not None else None
+    flags = torch.empty(1, device=dev, dtype=torch.int32) if want_flags else None
+    lib = _native.lib()
+    nsaved = lib.gpk_variational_saved_bytes(B, N, M, D) if (save and B > 0) else 0
+    saved = torch.empty((O or 1) * (nsaved // 4), device=dev, dtype=torch.float32) if nsaved > 0 else None
+    ins = (Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(), hyper.data_ptr())
+    if O is not None:        # one entry point, the state or NULL; no y / ell
+        name = "gpk_variational_batched_f32"
+        rc = lib.gpk_variational_batched_f32(X.data_ptr(), int(shared), *ins, O, B, N, M, D, mean.data_ptr(),
+                                             var.data_ptr(), _ptr(flags), _ptr(saved), _stream_ptr(dev))
+    elif saved is not None:
+        name = "gpk_variational_train_f32"
+        rc = lib.gpk_variational_train_f32(X.data_ptr(), *ins, _ptr(y), B, N, M, D, mean.data_ptr(),
+                                           var.data_ptr(), _ptr(ell), _ptr(flags), saved.data_ptr(),
+                                           _stream_ptr(dev))
+    else:
+        name = "gpk_variational_f32"
+        rc = lib.gpk_variational_f32(X.data_ptr(), *ins, _ptr(y), B, N, M, D, mean.data_ptr(),
+                                     var.data_ptr(), _ptr(ell), _ptr(flags), _stream_ptr(dev))
+    _native.check(rc, name)
+    return VariationalOut(mean, var, ell, flags, saved)
+
+
 def variational_forward(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
                         vstd: torch.Tensor, outputscale=None, noise=None, jitter=None, bias=None,
                         weights=None, lengthscale=None, y: Optional[torch.Tensor] = None,
@@ -644,50 +835,23 @@ def variational_forward(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vm
     ``save=True`` (training): where the saved-state adjoint serves the shape (M > 64), the
     forward also keeps A = Linv K_ZX and the clamp mask (gpk_variational_train_f32) in
     ``out.saved`` for ``variational_adjoint(..., saved=out.saved)``; None elsewhere."""
-    if X.dim() != 3:
-        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
-    B, N, D = X.shape
-    M = Z.shape[0]
-    if Z.shape != (M, D):
-        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
-    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
-    _require_device(X, Z, Linv, vmean, vstd)
-    dev = X.device
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vmean = vmean.detach().contiguous().float().reshape(-1)
-    vstd = vstd.detach().contiguous().float().reshape(-1)
+    _single_output(Z)
     if hyper is None:
-        hyper = pack_variational_hyper(outputscale, noise, jitter, bias, weights, lengthscale, D, dev)
-    if y is not None:
-        if y.shape != (B, N):
-            raise ValueError(f"y must be (B, N) = {(B, N)}, got {tuple(y.shape)}")
-        _require_device(y)
-        y = y.detach().contiguous().float()
-    mean = torch.empty(B, N, device=dev, dtype=torch.float32)
-    var = torch.empty(B, N, device=dev, dtype=torch.float32)
-    ell = torch.empty(B, device=dev, dtype=torch.float32) if y is not None else None
-    flags = torch.empty(1, device=dev, dtype=torch.int32) if want_flags else None
-    lib = _native.lib()
-    nsaved = lib.gpk_variational_saved_bytes(B, N, M, D) if (save and B > 0) else 0
-    if nsaved > 0:
-        saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
-        rc = lib.gpk_variational_train_f32(
-            X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-            hyper.data_ptr(), y.data_ptr() if y is not None else None, B, N, M, D,
-            mean.data_ptr(), var.data_ptr(), ell.data_ptr() if ell is not None else None,
-            flags.data_ptr() if flags is not None else None, saved.data_ptr(), _stream_ptr(dev))
-        _native.check(rc, "gpk_variational_train_f32")
-        return VariationalOut(mean, var, ell, flags, saved)
-    rc = lib.gpk_variational_f32(
-        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-        hyper.data_ptr(), y.data_ptr() if y is not None else None, B, N, M, D,
-        mean.data_ptr(), var.data_ptr(), ell.data_ptr() if ell is not None else None,
-        flags.data_ptr() if flags is not None else None, _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_f32")
-    return VariationalOut(mean, var, ell, flags)
+        hyper = pack_variational_hyper(outputscale, noise, jitter, bias, weights, lengthscale, X.shape[-1],
+                                       X.device)
+    return _variational_forward(X, Z, Linv, vmean, vstd, hyper, y, want_flags, save)
+
+
+def variational_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                                vstd: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
+                                save: bool = False) -> VariationalOut:
+    """``variational_forward`` for O outputs in one launch (gpk_variational_batched_f32): X
+    (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64,
+    vmean / vstd (O, M), hyper (O, 4 + 2D) -> mean, var (O, B, N), one clamp flag word for all
+    outputs and, with ``save`` where the saved-state adjoint serves the shape, the O training
+    states in ``out.saved``. Bit-identical to O single-output calls."""
+    _multi_output(Z)
+    return _variational_forward(X, Z, Linv, vmean, vstd, hyper, None, want_flags, save)
 
 
 @dataclass
@@ -704,195 +868,106 @@ class VariationalAdjoint:
     db0: torch.Tensor     # () LinearMean bias
 
 
+@dataclass
+class VariationalAdjointBatched:
+    dX: torch.Tensor      # (O, B, N, D) per output (shared inputs: the caller sums over O)
+    dLinv: torch.Tensor   # (O, M, M) float64, lower
+    dZ: torch.Tensor      # (O, M, D) the K_ZX part of dZ
+    dpar: torch.Tensor    # (O, 2M + 2D + 2): dvmean (M), dvstd (M), ds2, dls (D), dw (D), db0
+
+
+def _variational_adjoint(X, Z, Linv, vmean, vstd, hyper, gmean, gvar, saved):
+    """-> (dX, dLinv, dZ, dpar), every array with ``lead``."""
+    _require_device(X, Z, Linv, vmean, vstd, hyper, gmean, gvar)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper, cast_linv=True)
+    dev = X.device
+    vmean = _per_output(vmean, *lead, M)
+    vstd = _per_output(vstd, *lead, M)
+    gmean = _per_output(gmean, *lead, B, N)
+    gvar = _per_output(gvar, *lead, B, N)
+    lib = _native.lib()
+    if saved is not None:
+        # the C entry point receives a bare pointer: the dtype, device and size are checked here
+        if saved.dtype != torch.float32 or saved.device != dev:
+            raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device}): "
+                             f"pass the forward's (save=True) ``saved`` unchanged")
+        if saved.numel() * 4 != (O or 1) * lib.gpk_variational_saved_bytes(B, N, M, D):
+            raise ValueError("saved state does not match this shape (the forward's, with save=True)")
+        saved = saved.detach().contiguous()
+    # one output: an entry point and a workspace query per way; O outputs: one of each, has_saved
+    if O is not None:
+        name = "gpk_variational_adjoint_batched_f32"
+        nbytes = lib.gpk_variational_adjoint_batched_workspace_bytes(O, B, N, M, D, int(saved is not None))
+    elif saved is not None:
+        name = "gpk_variational_adjoint_saved_f32"
+        nbytes = lib.gpk_variational_adjoint_saved_workspace_bytes(B, N, M, D)
+    else:
+        name = "gpk_variational_adjoint_f32"
+        nbytes = lib.gpk_variational_adjoint_workspace_bytes(B, N, M, D)
+    if nbytes == 0:
+        raise ValueError(f"unsupported variational shape O={O} B={B} N={N} M={M} D={D}")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dX = torch.empty(*lead, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(*lead, 2 * M + 2 * D + 2, device=dev, dtype=torch.float32)
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    state = (_ptr(saved),) if (O is not None or saved is not None) else ()
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
+                            hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), *state, *dims, ws.data_ptr(),
+                            dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return dX, dLinv, dZ, dpar
+
+
 def variational_adjoint(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
                         vstd: torch.Tensor, hyper: torch.Tensor, gmean: torch.Tensor,
                         gvar: torch.Tensor, saved: Optional[torch.Tensor] = None) -> VariationalAdjoint:
     """Adjoint of ``variational_forward`` except the shared K_ZZ factor (fused gfx950
     kernels behind include/gpk.h::gpk_variational_adjoint_f32; from the training forward's
     ``saved`` state: gpk_variational_adjoint_saved_f32)."""
-    B, N, D = X.shape
-    M = Z.shape[0]
-    _require_device(X, Z, Linv, vmean, vstd, hyper, gmean, gvar)
-    dev = X.device
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous().double()
-    vmean = vmean.detach().reshape(M).contiguous().float()
-    vstd = vstd.detach().reshape(M).contiguous().float()
-    gmean = gmean.detach().reshape(B, N).contiguous().float()
-    gvar = gvar.detach().reshape(B, N).contiguous().float()
-    lib = _native.lib()
-    if saved is not None:
-        # the C entry point receives a bare pointer: the dtype and device are checked here
-        if saved.dtype != torch.float32 or saved.device != dev:
-            raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device}): "
-                             f"pass variational_forward(save=True).saved unchanged")
-        if saved.numel() * 4 != lib.gpk_variational_saved_bytes(B, N, M, D):
-            raise ValueError("saved state does not match this shape (variational_forward(save=True))")
-        nbytes = lib.gpk_variational_adjoint_saved_workspace_bytes(B, N, M, D)
-    else:
-        nbytes = lib.gpk_variational_adjoint_workspace_bytes(B, N, M, D)
-    if nbytes == 0:
-        raise ValueError(f"unsupported variational shape B={B} N={N} M={M} D={D}")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(2 * M + 2 * D + 2, device=dev, dtype=torch.float32)
-    if saved is not None:
-        _require_device(saved)
-        rc = lib.gpk_variational_adjoint_saved_f32(
-            X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-            hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), saved.detach().contiguous().data_ptr(),
-            B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(),
-            _stream_ptr(dev))
-        _native.check(rc, "gpk_variational_adjoint_saved_f32")
-    else:
-        rc = lib.gpk_variational_adjoint_f32(
-            X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-            hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), B, N, M, D, ws.data_ptr(),
-            dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), _stream_ptr(dev))
-        _native.check(rc, "gpk_variational_adjoint_f32")
+    _single_output(Z)
+    M, D = Z.shape
+    dX, dLinv, dZ, dpar = _variational_adjoint(X, Z, Linv, vmean, vstd, hyper, gmean, gvar, saved)
     return VariationalAdjoint(dX, dLinv, dpar, dZ, dpar[:M], dpar[M:2 * M], dpar[2 * M],
                               dpar[2 * M + 1:2 * M + 1 + D], dpar[2 * M + 1 + D:2 * M + 1 + 2 * D],
                               dpar[2 * M + 1 + 2 * D])
 
 
-def kzz_backward(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: torch.Tensor,
-                 outputscale: torch.Tensor, lengthscale: torch.Tensor):
-    """Back-propagate dObjective/dLinv (lower, fp64) through Linv = chol(K_ZZ + jitter)^{-1}
-    to (dZ, d outputscale, d lengthscale): once per optimizer step for all GP calls that
-    shared the factor (include/gpk.h::gpk_kzz_backward_f64: five fp64-MFMA tile GEMMs
-    Lbar = -tril(Linv^T G Linv^T), S = Linv^T Phi(L^T Lbar) Linv, then the RBF adjoint over
-    K_ZZ with Kbar = (S + S^T)/2). Returns (dZ (M, D) float, ds2 (), dls (D,)) -- dls per
-    dimension even for a shared lengthscale (the caller sums)."""
-    M, D = Z.shape
-    _require_device(dLinv, L, Linv, Z)
-    dev = Z.device
-    ls = lengthscale.detach().reshape(-1).float()
-    hyper = torch.cat([outputscale.detach().reshape(1).float(), ls.expand(D) if ls.numel() == 1 else ls])
-    lib = _native.lib()
-    ws = torch.empty(lib.gpk_kzz_backward_workspace_bytes(M, D), device=dev, dtype=torch.uint8)
-    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
-    dhyp = torch.empty(1 + D, device=dev, dtype=torch.float32)
-    rc = lib.gpk_kzz_backward_f64(dLinv.detach().contiguous().double().data_ptr(),
-                                  L.detach().contiguous().data_ptr(), Linv.detach().contiguous().data_ptr(),
-                                  Z.detach().contiguous().float().data_ptr(), hyper.data_ptr(), M, D,
-                                  ws.data_ptr(), dZ.data_ptr(), dhyp.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_kzz_backward_f64")
-    return dZ, dhyp[0], dhyp[1:]
+def variational_adjoint_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                                vstd: torch.Tensor, hyper: torch.Tensor, gmean: torch.Tensor,
+                                gvar: torch.Tensor,
+                                saved: Optional[torch.Tensor] = None) -> VariationalAdjointBatched:
+    """``variational_adjoint`` for O outputs, every launch once
+    (gpk_variational_adjoint_batched_f32); arguments as ``variational_forward_batched`` plus
+    gmean / gvar (O, B, N) and the forward's ``saved`` state (None: recompute)."""
+    _multi_output(Z)
+    return VariationalAdjointBatched(*_variational_adjoint(X, Z, Linv, vmean, vstd, hyper, gmean, gvar, saved))
 
 
-# ---------------------------------------------------------------------------
-# Multi-output (batched) variational chain: O independent GPs in one launch of every kernel
-# (include/gpk.h::gpk_*_batched; ToyDeepGPHiddenLayer(output_dims=O), DeepGP.py:24-31)
-# ---------------------------------------------------------------------------
-def kzz_cholesky_batched(Z: torch.Tensor, hyper: torch.Tensor, jitter: float = 1e-4,
-                         chol_jitter: float = 1e-8, max_tries: int = 3) -> KzzFactor:
-    """The K_ZZ factors of O outputs (include/gpk.h::gpk_kzz_chol_f64_batched): Z (O, M, D),
-    hyper (O, 1 + D) = {outputscale, lengthscale[D]} per output -> L, Linv (O, M, M) float64
-    and info (O,), bit-identical to O ``kzz_cholesky`` calls."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    _require_device(Z, hyper)
-    Z = Z.detach().contiguous().float()
-    O, M, D = Z.shape
-    dev = Z.device
-    if tuple(hyper.shape) != (O, 1 + D):
-        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
-    hyper = hyper.detach().contiguous().float()
-    L = torch.empty(O, M, M, device=dev, dtype=torch.float64)
-    Linv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
-    info = torch.empty(O, device=dev, dtype=torch.int32)
-    rc = _native.lib().gpk_kzz_chol_f64_batched(Z.data_ptr(), hyper.data_ptr(), O, M, D, float(jitter),
-                                                float(chol_jitter), int(max_tries), L.data_ptr(),
-                                                Linv.data_ptr(), info.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_kzz_chol_f64_batched")
-    return KzzFactor(L, Linv, info)
-
-
-def kzz_backward_batched(dLinv: torch.Tensor, L: torch.Tensor, Linv: torch.Tensor, Z: torch.Tensor,
-                         hyper: torch.Tensor):
-    """``kzz_backward`` for O outputs, every launch once (gpk_kzz_backward_f64_batched):
-    dLinv, L, Linv (O, M, M) float64, Z (O, M, D), hyper (O, 1 + D) -> (dZ (O, M, D),
-    dhyp (O, 1 + D) = {ds2, dlengthscale[D]} per output)."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    for name, t in (("dLinv", dLinv), ("L", L), ("Linv", Linv)):
-        if tuple(t.shape) != (O, M, M):
-            raise ValueError(f"{name} must be (O, M, M) = {(O, M, M)}, got {tuple(t.shape)}")
-    if tuple(hyper.shape) != (O, 1 + D):
-        raise ValueError(f"kzz hyper must be (O, 1 + D) = {(O, 1 + D)}, got {tuple(hyper.shape)}")
-    _require_device(dLinv, L, Linv, Z, hyper)
-    dev = Z.device
-    lib = _native.lib()
-    nbytes = lib.gpk_kzz_backward_batched_workspace_bytes(O, M, D)
-    if nbytes == 0:
-        raise ValueError(f"unsupported K_ZZ shape O={O} M={M} D={D}")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
-    dhyp = torch.empty(O, 1 + D, device=dev, dtype=torch.float32)
-    rc = lib.gpk_kzz_backward_f64_batched(
-        dLinv.detach().contiguous().double().data_ptr(), L.detach().contiguous().double().data_ptr(),
-        Linv.detach().contiguous().double().data_ptr(), Z.detach().contiguous().float().data_ptr(),
-        hyper.detach().contiguous().float().data_ptr(), O, M, D, ws.data_ptr(), dZ.data_ptr(),
-        dhyp.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_kzz_backward_f64_batched")
-    return dZ, dhyp
-
-
-def _batched_x(X: torch.Tensor, O: int):
-    """(contiguous float X, shared flag): X (B, N, D) is read by every output; an (O, B, N, D)
-    tensor whose output dimension is an expansion (stride 0) too, without a copy."""
-    if X.dim() == 3:
-        return X.detach().contiguous().float(), True
-    if X.dim() != 4 or X.shape[0] != O:
-        raise ValueError(f"X must be (B, N, D) or (O, B, N, D) with O = {O}, got {tuple(X.shape)}")
-    if O > 1 and X.stride(0) == 0:
-        return X[0].detach().contiguous().float(), True
-    return X.detach().contiguous().float(), False
-
-
-def variational_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
-                                vstd: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
-                                save: bool = False) -> VariationalOut:
-    """``variational_forward`` for O outputs in one launch (gpk_variational_batched_f32): X
-    (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64,
-    vmean / vstd (O, M), hyper (O, 4 + 2D) -> mean, var (O, B, N), one clamp flag word for all
-    outputs and, with ``save`` where the saved-state adjoint serves the shape, the O training
-    states in ``out.saved``. Bit-identical to O single-output calls."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    _require_device(X, Z, Linv, vmean, vstd, hyper)
-    X, shared = _batched_x(X, O)
-    B, N = X.shape[-3], X.shape[-2]
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
-    if tuple(hyper.shape) != (O, 4 + 2 * D):
-        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
+def _variational_cov(X, Z, Linv, vstd, hyper, return_state):
+    _require_device(X, Z, Linv, vstd, hyper)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
     dev = X.device
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vmean = vmean.detach().reshape(O, M).contiguous().float()
-    vstd = vstd.detach().reshape(O, M).contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    mean = torch.empty(O, B, N, device=dev, dtype=torch.float32)
-    var = torch.empty(O, B, N, device=dev, dtype=torch.float32)
-    flags = torch.empty(1, device=dev, dtype=torch.int32) if want_flags else None
+    vstd = _per_output(vstd, *lead, M)
     lib = _native.lib()
-    nsaved = lib.gpk_variational_saved_bytes(B, N, M, D) if (save and B > 0) else 0
-    saved = torch.empty(O * (nsaved // 4), device=dev, dtype=torch.float32) if nsaved > 0 else None
-    rc = lib.gpk_variational_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-        hyper.data_ptr(), O, B, N, M, D, mean.data_ptr(), var.data_ptr(),
-        flags.data_ptr() if flags is not None else None, saved.data_ptr() if saved is not None else None,
-        _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_batched_f32")
-    return VariationalOut(mean, var, None, flags, saved)
+    if O is None:
+        name = "gpk_variational_cov_f32"
+        nbytes = lib.gpk_variational_cov_workspace_bytes(B, N, M)
+    else:
+        name = "gpk_variational_cov_batched_f32"
+        nbytes = lib.gpk_variational_cov_batched_workspace_bytes(O, B, N, M)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}")
+    cov = torch.empty(*lead, B, N, N, device=dev, dtype=torch.float32)
+    if B == 0:
+        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), *dims,
+                            ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return (cov, ws) if return_state else cov
 
 
 def variational_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
@@ -903,38 +978,8 @@ def variational_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: 
     vector (pack_variational_hyper). Memory per call: the A workspace (B * M * N floats, N
     rounded up to 64, + 64 B) lives only for the call; the result is B * N^2 floats.
     ``return_state``: -> (cov, workspace), the saved state ``variational_cov_grad`` runs from."""
-    if X.dim() != 3:
-        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
-    B, N, D = X.shape
-    M = Z.shape[0]
-    if Z.shape != (M, D):
-        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
-    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
-    if hyper.numel() != 4 + 2 * D:
-        raise ValueError(f"hyper must have 4 + 2D = {4 + 2 * D} entries, got {hyper.numel()}")
-    _require_device(X, Z, Linv, vstd, hyper)
-    dev = X.device
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vstd = vstd.detach().contiguous().float().reshape(-1)
-    hyper = hyper.detach().contiguous().float()
-    if vstd.numel() != M:
-        raise ValueError(f"vstd must have M = {M} entries, got {vstd.numel()}")
-    lib = _native.lib()
-    nbytes = lib.gpk_variational_cov_workspace_bytes(B, N, M)
-    if nbytes == 0 and B > 0:
-        raise ValueError(f"gpk_variational_cov_f32 does not support B={B}, N={N}, M={M}")
-    cov = torch.empty(B, N, N, device=dev, dtype=torch.float32)
-    if B == 0:
-        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
-    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_cov_f32(X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(),
-                                     hyper.data_ptr(), B, N, M, D, ws.data_ptr(), cov.data_ptr(),
-                                     _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_cov_f32")
-    return (cov, ws) if return_state else cov
+    _single_output(Z)
+    return _variational_cov(X, Z, Linv, vstd, hyper, return_state)
 
 
 def variational_cov_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
@@ -944,48 +989,51 @@ def variational_cov_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor
     (O, M), hyper (O, 4 + 2D) -> cov (O, B, N, N). Bit-identical to O single-output calls.
     Memory per call: O workspaces of ``variational_cov`` + the O * B * N^2 floats of cov.
     ``return_state``: -> (cov, workspace), the saved state of ``variational_cov_grad_batched``."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    _require_device(X, Z, Linv, vstd, hyper)
-    X, shared = _batched_x(X, O)
-    B, N = X.shape[-3], X.shape[-2]
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
-    if tuple(hyper.shape) != (O, 4 + 2 * D):
-        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
-    dev = X.device
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vstd = vstd.detach().reshape(O, M).contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    lib = _native.lib()
-    nbytes = lib.gpk_variational_cov_batched_workspace_bytes(O, B, N, M)
-    if nbytes == 0 and B > 0:
-        raise ValueError(f"gpk_variational_cov_batched_f32 does not support O={O}, B={B}, N={N}, M={M}")
-    cov = torch.empty(O, B, N, N, device=dev, dtype=torch.float32)
-    if B == 0:
-        return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
-    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_cov_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), O, B,
-        N, M, D, ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_cov_batched_f32")
-    return (cov, ws) if return_state else cov
+    _multi_output(Z)
+    return _variational_cov(X, Z, Linv, vstd, hyper, return_state)
 
 
-def _cov_grad_state(state, lib, O, B, N, M, dev):
-    """The forward's workspace, as ``variational_cov(..., return_state=True)`` returned it: the C
-    entry point receives a bare pointer, so its dtype, device and size are checked here."""
-    if state.dtype != torch.float32 or state.device != dev:
-        raise ValueError(f"state must be float32 on {dev} (got {state.dtype} on {state.device}): pass "
-                         f"variational_cov(return_state=True)'s workspace unchanged")
-    want = (lib.gpk_variational_cov_workspace_bytes(B, N, M) // 4) * O
-    if state.numel() != max(1, want):
-        raise ValueError(f"state has {state.numel()} floats, this shape's forward workspace has {want}")
+def _cov_grad_state(state, nfloats, dev, source: str):
+    """The forward's workspace, as ``source`` (return_state=True) returned it: the C entry point
+    receives a bare pointer, so its dtype, device and size are checked here."""
+    if state.dtype != torch.float32 or state.device != dev or state.numel() != max(1, nfloats):
+        raise ValueError(f"state must be the {nfloats} float32 values on {dev} that {source}(return_state=True) "
+                         f"returned for this shape, got {state.numel()} {state.dtype} on {state.device}")
     return state.detach().contiguous()
+
+
+def _variational_cov_grad(X, Z, Linv, vstd, hyper, state, gcov):
+    _require_device(X, Z, Linv, vstd, hyper, state, gcov)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
+    dev = X.device
+    if tuple(gcov.shape) != lead + (B, N, N):
+        raise ValueError(f"gcov must be {lead + (B, N, N)}, got {tuple(gcov.shape)}")
+    vstd = _per_output(vstd, *lead, M)
+    gcov = gcov.detach().contiguous().float()
+    lib = _native.lib()
+    if O is None:
+        name = "gpk_variational_cov_grad_f32"
+        nbytes = lib.gpk_variational_cov_grad_workspace_bytes(B, N, M, D)
+    else:
+        name = "gpk_variational_cov_grad_batched_f32"
+        nbytes = lib.gpk_variational_cov_grad_batched_workspace_bytes(O, B, N, M, D)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+    dX = torch.empty(*lead, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(*lead, M + 1 + D, device=dev, dtype=torch.float32)
+    if B == 0:
+        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_()
+    state = _cov_grad_state(state, (O or 1) * (lib.gpk_variational_cov_workspace_bytes(B, N, M) // 4), dev,
+                            "variational_cov")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(),
+                            state.data_ptr(), gcov.data_ptr(), *dims, ws.data_ptr(), dX.data_ptr(),
+                            dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return dX, dLinv, dZ, dpar
 
 
 def variational_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
@@ -995,46 +1043,8 @@ def variational_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, v
     workspace ``state`` returns (dX (B, N, D), dLinv (M, M) float64 lower, dZ (M, D), dpar
     (M + 1 + D) = [dvstd, ds2, dlengthscale]). Memory per call: the workspace (2 B M N floats, N
     rounded up to 64, + min(B, 32) M^2 doubles) lives only for the call."""
-    if X.dim() != 3:
-        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
-    B, N, D = X.shape
-    M = Z.shape[0]
-    if Z.shape != (M, D):
-        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
-    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
-    if hyper.numel() != 4 + 2 * D:
-        raise ValueError(f"hyper must have 4 + 2D = {4 + 2 * D} entries, got {hyper.numel()}")
-    if tuple(gcov.shape) != (B, N, N):
-        raise ValueError(f"gcov must be (B, N, N) = {(B, N, N)}, got {tuple(gcov.shape)}")
-    _require_device(X, Z, Linv, vstd, hyper, state, gcov)
-    dev = X.device
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vstd = vstd.detach().contiguous().float().reshape(-1)
-    hyper = hyper.detach().contiguous().float()
-    gcov = gcov.detach().contiguous().float()
-    if vstd.numel() != M:
-        raise ValueError(f"vstd must have M = {M} entries, got {vstd.numel()}")
-    lib = _native.lib()
-    nbytes = lib.gpk_variational_cov_grad_workspace_bytes(B, N, M, D)
-    if nbytes == 0 and B > 0:
-        raise ValueError(f"gpk_variational_cov_grad_f32 does not support B={B}, N={N}, M={M}, D={D}")
-    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(M + 1 + D, device=dev, dtype=torch.float32)
-    if B == 0:
-        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_()
-    state = _cov_grad_state(state, lib, 1, B, N, M, dev)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    rc = lib.gpk_variational_cov_grad_f32(
-        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(), state.data_ptr(),
-        gcov.data_ptr(), B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(),
-        dpar.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_cov_grad_f32")
-    return dX, dLinv, dZ, dpar
+    _single_output(Z)
+    return _variational_cov_grad(X, Z, Linv, vstd, hyper, state, gcov)
 
 
 def variational_cov_grad_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vstd: torch.Tensor,
@@ -1044,45 +1054,8 @@ def variational_cov_grad_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.T
     workspace ``state`` and gcov (O, B, N, N) -> (dX (O, B, N, D) per output, also with shared
     inputs: the caller sums over O; dLinv (O, M, M) float64, dZ (O, M, D), dpar (O, M + 1 + D)).
     Bit-identical to O single-output calls."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    _require_device(X, Z, Linv, vstd, hyper, state, gcov)
-    X, shared = _batched_x(X, O)
-    B, N = X.shape[-3], X.shape[-2]
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
-    if tuple(hyper.shape) != (O, 4 + 2 * D):
-        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
-    if tuple(gcov.shape) != (O, B, N, N):
-        raise ValueError(f"gcov must be (O, B, N, N) = {(O, B, N, N)}, got {tuple(gcov.shape)}")
-    dev = X.device
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vstd = vstd.detach().reshape(O, M).contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    gcov = gcov.detach().contiguous().float()
-    lib = _native.lib()
-    nbytes = lib.gpk_variational_cov_grad_batched_workspace_bytes(O, B, N, M, D)
-    if nbytes == 0 and B > 0:
-        raise ValueError(f"gpk_variational_cov_grad_batched_f32 does not support O={O}, B={B}, N={N}, "
-                         f"M={M}, D={D}")
-    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(O, M + 1 + D, device=dev, dtype=torch.float32)
-    if B == 0:
-        return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_()
-    state = _cov_grad_state(state, lib, O, B, N, M, dev)
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    rc = lib.gpk_variational_cov_grad_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vstd.data_ptr(), hyper.data_ptr(),
-        state.data_ptr(), gcov.data_ptr(), O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(),
-        dZ.data_ptr(), dpar.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_cov_grad_batched_f32")
-    return dX, dLinv, dZ, dpar
+    _multi_output(Z)
+    return _variational_cov_grad(X, Z, Linv, vstd, hyper, state, gcov)
 
 
 MVN_ROOT_MAX_N = 256   # gpk_mvn_root_max_n(): the matrix lives in one workgroup's LDS
@@ -1220,67 +1193,6 @@ def mvn_root_grad(R: torch.Tensor, gR: Optional[torch.Tensor] = None, gsamples: 
     return dcov, dmean
 
 
-@dataclass
-class VariationalAdjointBatched:
-    dX: torch.Tensor      # (O, B, N, D) per output (shared inputs: the caller sums over O)
-    dLinv: torch.Tensor   # (O, M, M) float64, lower
-    dZ: torch.Tensor      # (O, M, D) the K_ZX part of dZ
-    dpar: torch.Tensor    # (O, 2M + 2D + 2): dvmean (M), dvstd (M), ds2, dls (D), dw (D), db0
-
-
-def variational_adjoint_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
-                                vstd: torch.Tensor, hyper: torch.Tensor, gmean: torch.Tensor,
-                                gvar: torch.Tensor,
-                                saved: Optional[torch.Tensor] = None) -> VariationalAdjointBatched:
-    """``variational_adjoint`` for O outputs, every launch once
-    (gpk_variational_adjoint_batched_f32); arguments as ``variational_forward_batched`` plus
-    gmean / gvar (O, B, N) and the forward's ``saved`` state (None: recompute)."""
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    _require_device(X, Z, Linv, vmean, vstd, hyper, gmean, gvar)
-    X, shared = _batched_x(X, O)
-    B, N = X.shape[-3], X.shape[-2]
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != (O, M, M):
-        raise ValueError(f"Linv must be (O, M, M) = {(O, M, M)}, got {tuple(Linv.shape)}")
-    if tuple(hyper.shape) != (O, 4 + 2 * D):
-        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
-    dev = X.device
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous().double()
-    vmean = vmean.detach().reshape(O, M).contiguous().float()
-    vstd = vstd.detach().reshape(O, M).contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    gmean = gmean.detach().reshape(O, B, N).contiguous().float()
-    gvar = gvar.detach().reshape(O, B, N).contiguous().float()
-    lib = _native.lib()
-    if saved is not None:
-        # the C entry point receives a bare pointer: the dtype and device are checked here
-        if saved.dtype != torch.float32 or saved.device != dev:
-            raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device}): "
-                             f"pass variational_forward_batched(save=True).saved unchanged")
-        if saved.numel() * 4 != O * lib.gpk_variational_saved_bytes(B, N, M, D):
-            raise ValueError("saved state does not match this shape (variational_forward_batched(save=True))")
-        saved = saved.detach().contiguous()
-    nbytes = lib.gpk_variational_adjoint_batched_workspace_bytes(O, B, N, M, D, int(saved is not None))
-    if nbytes == 0:
-        raise ValueError(f"unsupported variational shape O={O} B={B} N={N} M={M} D={D}")
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(O, 2 * M + 2 * D + 2, device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_adjoint_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vstd.data_ptr(),
-        hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), saved.data_ptr() if saved is not None else None,
-        O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(),
-        _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_adjoint_batched_f32")
-    return VariationalAdjointBatched(dX, dLinv, dZ, dpar)
-
-
 # ---------------------------------------------------------------------------
 # ELBO terms (gpk_gauss_ell_f32 / gpk_meanfield_kl_f32)
 # ---------------------------------------------------------------------------
@@ -1384,7 +1296,8 @@ def variational_elbo_grad(y, mean, var, noise, vmean, vstd, kl_scale: float, gel
 
 
 # ---------------------------------------------------------------------------
-# Cholesky (full-covariance) q(u): gpk_variational_chol_f32 / _adjoint_f32, gpk_cholesky_kl_f32
+# Cholesky (full-covariance) q(u): gpk_variational_chol_f32 / _adjoint_f32, gpk_cholesky_kl_f32 and
+# their batched forms (the output index on grid y of every launch); the same convention as above
 # ---------------------------------------------------------------------------
 def variational_chol_supported(B: int, N: int, M: int, D: int, adjoint: bool = False) -> bool:
     """Whether the Cholesky-q(u) kernels serve the shape (the *_bytes queries of include/gpk.h:
@@ -1397,119 +1310,6 @@ def variational_chol_supported(B: int, N: int, M: int, D: int, adjoint: bool = F
     return lib.gpk_variational_chol_saved_bytes(B, N, M, D) > 0
 
 
-@dataclass
-class VariationalCholOut:
-    mean: torch.Tensor             # (B, N)
-    var: torch.Tensor              # (B, N) clamped at 1e-6
-    flags: Optional[torch.Tensor]  # (1,) int32: bit 0 = the variance clamp fired
-    saved: Optional[torch.Tensor]  # A = Linv K_ZX (B, M, as) and the clamp mask (B, as), or None
-
-
-def variational_chol_forward(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
-                             vchol: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
-                             save: bool = False) -> VariationalCholOut:
-    """Batched q(f) mean / variance of the whitened VariationalStrategy with a Cholesky q(u)
-    (include/gpk.h::gpk_variational_chol_f32); ``hyper`` is pack_variational_hyper's vector.
-    ``save=True`` keeps A and the clamp mask for ``variational_chol_adjoint``."""
-    if X.dim() != 3:
-        raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
-    B, N, D = X.shape
-    M = Z.shape[0]
-    if Z.shape != (M, D):
-        raise ValueError(f"Z must be (M, {D}), got {tuple(Z.shape)}")
-    if Linv.shape != (M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (M, M) float64 from kzz_cholesky")
-    if vchol.shape != (M, M):
-        raise ValueError(f"chol_variational_covar must be ({M}, {M}), got {tuple(vchol.shape)}")
-    _require_device(X, Z, Linv, vmean, vchol, hyper)
-    dev = X.device
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous()
-    vmean = vmean.detach().contiguous().float().reshape(-1)
-    vchol = vchol.detach().contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    mean = torch.empty(B, N, device=dev, dtype=torch.float32)
-    var = torch.empty(B, N, device=dev, dtype=torch.float32)
-    flags = torch.zeros(1, device=dev, dtype=torch.int32) if want_flags else None
-    lib = _native.lib()
-    saved = None
-    if B > 0:
-        nsaved = lib.gpk_variational_chol_saved_bytes(B, N, M, D)
-        if nsaved == 0:
-            raise ValueError(f"gpk_variational_chol_f32 does not support B={B}, N={N}, M={M}, D={D}")
-        if save:
-            saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_chol_f32(
-        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
-        B, N, M, D, mean.data_ptr(), var.data_ptr(), flags.data_ptr() if flags is not None else None,
-        saved.data_ptr() if saved is not None else None, _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_f32")
-    return VariationalCholOut(mean, var, flags, saved)
-
-
-def variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
-    """Adjoint of ``variational_chol_forward`` except the shared K_ZZ factor
-    (include/gpk.h::gpk_variational_chol_adjoint_f32) -> (dX (B, N, D), dLinv (M, M) float64 lower,
-    dZ (M, D), dpar (M + 2D + 2) = [dvmean, ds2, dls, dw, db0], dchol (M, M) lower)."""
-    B, N, D = X.shape
-    M = Z.shape[0]
-    _require_device(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
-    dev = X.device
-    lib = _native.lib()
-    if saved.dtype != torch.float32 or saved.device != dev:
-        raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device})")
-    if saved.numel() * 4 != lib.gpk_variational_chol_saved_bytes(B, N, M, D):
-        raise ValueError("saved state does not match this shape (variational_chol_forward(save=True))")
-    nbytes = lib.gpk_variational_chol_adjoint_workspace_bytes(B, N, M, D)
-    if nbytes == 0:
-        raise ValueError(f"gpk_variational_chol_adjoint_f32 does not support B={B}, N={N}, M={M}, D={D}")
-    X = X.detach().contiguous().float()
-    Z = Z.detach().contiguous().float()
-    Linv = Linv.detach().contiguous().double()
-    vmean = vmean.detach().reshape(M).contiguous().float()
-    vchol = vchol.detach().contiguous().float()
-    hyper = hyper.detach().contiguous().float()
-    gmean = gmean.detach().reshape(B, N).contiguous().float()
-    gvar = gvar.detach().reshape(B, N).contiguous().float()
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    dX = torch.empty(B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(M + 2 * D + 2, device=dev, dtype=torch.float32)
-    dchol = torch.empty(M, M, device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_chol_adjoint_f32(
-        X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
-        gmean.data_ptr(), gvar.data_ptr(), saved.detach().contiguous().data_ptr(), B, N, M, D, ws.data_ptr(),
-        dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_adjoint_f32")
-    return dX, dLinv, dZ, dpar, dchol
-
-
-def cholesky_kl(m: torch.Tensor, chol: torch.Tensor) -> torch.Tensor:
-    """KL(N(m, L L^T) || N(0, I)), L = tril(chol), as a (1,) tensor (one launch)."""
-    _require_device(m, chol)
-    kl = torch.empty(1, device=m.device, dtype=torch.float32)
-    rc = _native.lib().gpk_cholesky_kl_f32(m.data_ptr(), chol.data_ptr(), m.numel(), kl.data_ptr(), None, None,
-                                           None, _stream_ptr(m.device))
-    _native.check(rc, "gpk_cholesky_kl_f32")
-    return kl
-
-
-def cholesky_kl_grad(m, chol, gkl):
-    _require_device(m, chol, gkl)
-    dm = torch.empty_like(m)
-    dchol = torch.empty_like(chol)
-    rc = _native.lib().gpk_cholesky_kl_f32(m.data_ptr(), chol.data_ptr(), m.numel(), None, gkl.data_ptr(),
-                                           dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
-    _native.check(rc, "gpk_cholesky_kl_f32")
-    return dm, dchol
-
-
-# ---------------------------------------------------------------------------
-# Cholesky q(u) for O outputs at once: gpk_variational_chol_batched_f32 / _adjoint_batched_f32,
-# gpk_cholesky_kl_batched_f32 (the output index on grid y of every launch)
-# ---------------------------------------------------------------------------
 def variational_chol_batched_supported(O: int, B: int, N: int, M: int, D: int, adjoint: bool = False) -> bool:
     """Whether the batched Cholesky-q(u) kernels serve the shape (the two batched *_bytes
     queries: 1 <= O <= 65535 and the single-output bounds)."""
@@ -1521,22 +1321,54 @@ def variational_chol_batched_supported(O: int, B: int, N: int, M: int, D: int, a
     return lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D) > 0
 
 
-def _chol_batched_args(X, Z, Linv, vmean, vchol, hyper):
-    if Z.dim() != 3:
-        raise ValueError(f"Z must be (O, M, D), got {tuple(Z.shape)}")
-    O, M, D = Z.shape
-    X, shared = _batched_x(X, O)
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (O, M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != (O, M, M) or Linv.dtype != torch.float64:
-        raise ValueError("Linv must be (O, M, M) float64 from kzz_cholesky_batched")
-    if tuple(vchol.shape) != (O, M, M):
-        raise ValueError(f"chol_variational_covar must be {(O, M, M)}, got {tuple(vchol.shape)}")
-    if tuple(hyper.shape) != (O, 4 + 2 * D):
-        raise ValueError(f"hyper must be (O, 4 + 2D) = {(O, 4 + 2 * D)}, got {tuple(hyper.shape)}")
-    return (X, shared, Z.detach().contiguous().float(), Linv.detach().contiguous(),
-            vmean.detach().reshape(O, M).contiguous().float(), vchol.detach().contiguous().float(),
-            hyper.detach().contiguous().float())
+@dataclass
+class VariationalCholOut:
+    mean: torch.Tensor             # (B, N); (O, B, N) for O outputs
+    var: torch.Tensor              # as mean, clamped at 1e-6
+    flags: Optional[torch.Tensor]  # (1,) int32: bit 0 = the variance clamp fired
+    saved: Optional[torch.Tensor]  # A = Linv K_ZX (B, M, as) and the clamp mask (B, as) per output, or None
+
+
+def _chol_saved_bytes(lib, O, B, N, M, D) -> int:
+    if O is None:
+        return lib.gpk_variational_chol_saved_bytes(B, N, M, D)
+    return lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D)
+
+
+def _variational_chol_forward(X, Z, Linv, vmean, vchol, hyper, want_flags, save) -> VariationalCholOut:
+    _require_device(X, Z, Linv, vmean, vchol, hyper)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
+    dev = X.device
+    vmean = _per_output(vmean, *lead, M)
+    vchol = _vchol_arg(vchol, lead, M)
+    mean = torch.empty(*lead, B, N, device=dev, dtype=torch.float32)
+    var = torch.empty(*lead, B, N, device=dev, dtype=torch.float32)
+    flags = torch.zeros(1, device=dev, dtype=torch.int32) if want_flags else None
+    lib = _native.lib()
+    name = "gpk_variational_chol_f32" if O is None else "gpk_variational_chol_batched_f32"
+    saved = None
+    if B > 0:
+        nsaved = _chol_saved_bytes(lib, O, B, N, M, D)
+        if nsaved == 0:
+            raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+        if save:
+            saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
+                            hyper.data_ptr(), *dims, mean.data_ptr(), var.data_ptr(), _ptr(flags), _ptr(saved),
+                            _stream_ptr(dev))
+    _native.check(rc, name)
+    return VariationalCholOut(mean, var, flags, saved)
+
+
+def variational_chol_forward(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
+                             vchol: torch.Tensor, hyper: torch.Tensor, want_flags: bool = True,
+                             save: bool = False) -> VariationalCholOut:
+    """Batched q(f) mean / variance of the whitened VariationalStrategy with a Cholesky q(u)
+    (include/gpk.h::gpk_variational_chol_f32); ``hyper`` is pack_variational_hyper's vector.
+    ``save=True`` keeps A and the clamp mask for ``variational_chol_adjoint``."""
+    _single_output(Z)
+    return _variational_chol_forward(X, Z, Linv, vmean, vchol, hyper, want_flags, save)
 
 
 def variational_chol_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vmean: torch.Tensor,
@@ -1546,65 +1378,94 @@ def variational_chol_forward_batched(X: torch.Tensor, Z: torch.Tensor, Linv: tor
     X (B, N, D) shared by every output or (O, B, N, D), Z (O, M, D), Linv (O, M, M) float64, vmean
     (O, M), vchol (O, M, M), hyper (O, 4 + 2D) -> mean, var (O, B, N), one clamp flag word for all
     outputs and, with ``save``, the O states. Bit-identical to O single-output calls."""
-    _require_device(X, Z, Linv, vmean, vchol, hyper)
-    X, shared, Z, Linv, vmean, vchol, hyper = _chol_batched_args(X, Z, Linv, vmean, vchol, hyper)
-    O, M, D = Z.shape
-    B, N = X.shape[-3], X.shape[-2]
+    _multi_output(Z)
+    return _variational_chol_forward(X, Z, Linv, vmean, vchol, hyper, want_flags, save)
+
+
+def _variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
+    _require_device(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper, cast_linv=True)
     dev = X.device
-    mean = torch.empty(O, B, N, device=dev, dtype=torch.float32)
-    var = torch.empty(O, B, N, device=dev, dtype=torch.float32)
-    flags = torch.zeros(1, device=dev, dtype=torch.int32) if want_flags else None
     lib = _native.lib()
-    saved = None
-    if B > 0:
-        nsaved = lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D)
-        if nsaved == 0:
-            raise ValueError(f"gpk_variational_chol_batched_f32 does not support O={O}, B={B}, N={N}, M={M}, "
-                             f"D={D}")
-        if save:
-            saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_chol_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
-        hyper.data_ptr(), O, B, N, M, D, mean.data_ptr(), var.data_ptr(),
-        flags.data_ptr() if flags is not None else None, saved.data_ptr() if saved is not None else None,
-        _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_batched_f32")
-    return VariationalCholOut(mean, var, flags, saved)
+    if saved.dtype != torch.float32 or saved.device != dev:
+        raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device})")
+    if saved.numel() * 4 != _chol_saved_bytes(lib, O, B, N, M, D):
+        raise ValueError("saved state does not match this shape (the forward's, with save=True)")
+    if O is None:
+        name = "gpk_variational_chol_adjoint_f32"
+        nbytes = lib.gpk_variational_chol_adjoint_workspace_bytes(B, N, M, D)
+    else:
+        name = "gpk_variational_chol_adjoint_batched_f32"
+        nbytes = lib.gpk_variational_chol_adjoint_batched_workspace_bytes(O, B, N, M, D)
+    if nbytes == 0:
+        raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+    vmean = _per_output(vmean, *lead, M)
+    vchol = _vchol_arg(vchol, lead, M)
+    gmean = _per_output(gmean, *lead, B, N)
+    gvar = _per_output(gvar, *lead, B, N)
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    dX = torch.empty(*lead, B, N, D, device=dev, dtype=torch.float32)
+    dLinv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
+    dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
+    dpar = torch.empty(*lead, M + 2 * D + 2, device=dev, dtype=torch.float32)
+    dchol = torch.empty(*lead, M, M, device=dev, dtype=torch.float32)
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
+                            hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(),
+                            saved.detach().contiguous().data_ptr(), *dims, ws.data_ptr(), dX.data_ptr(),
+                            dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
+    return dX, dLinv, dZ, dpar, dchol
+
+
+def variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
+    """Adjoint of ``variational_chol_forward`` except the shared K_ZZ factor
+    (include/gpk.h::gpk_variational_chol_adjoint_f32) -> (dX (B, N, D), dLinv (M, M) float64 lower,
+    dZ (M, D), dpar (M + 2D + 2) = [dvmean, ds2, dls, dw, db0], dchol (M, M) lower)."""
+    _single_output(Z)
+    return _variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
 
 
 def variational_chol_adjoint_batched(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved):
     """``variational_chol_adjoint`` for O outputs, every launch once
     (gpk_variational_chol_adjoint_batched_f32) -> (dX (O, B, N, D) per output also with shared
     inputs, dLinv (O, M, M) float64 lower, dZ (O, M, D), dpar (O, M + 2D + 2), dchol (O, M, M))."""
-    _require_device(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
-    X, shared, Z, Linv, vmean, vchol, hyper = _chol_batched_args(X, Z, Linv.double(), vmean, vchol, hyper)
-    O, M, D = Z.shape
-    B, N = X.shape[-3], X.shape[-2]
-    dev = X.device
-    lib = _native.lib()
-    if saved.dtype != torch.float32 or saved.device != dev:
-        raise ValueError(f"saved state must be float32 on {dev} (got {saved.dtype} on {saved.device})")
-    if saved.numel() * 4 != lib.gpk_variational_chol_batched_saved_bytes(O, B, N, M, D):
-        raise ValueError("saved state does not match this shape (variational_chol_forward_batched(save=True))")
-    nbytes = lib.gpk_variational_chol_adjoint_batched_workspace_bytes(O, B, N, M, D)
-    if nbytes == 0:
-        raise ValueError(f"gpk_variational_chol_adjoint_batched_f32 does not support O={O}, B={B}, N={N}, "
-                         f"M={M}, D={D}")
-    gmean = gmean.detach().reshape(O, B, N).contiguous().float()
-    gvar = gvar.detach().reshape(O, B, N).contiguous().float()
-    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    dX = torch.empty(O, B, N, D, device=dev, dtype=torch.float32)
-    dLinv = torch.empty(O, M, M, device=dev, dtype=torch.float64)
-    dZ = torch.empty(O, M, D, device=dev, dtype=torch.float32)
-    dpar = torch.empty(O, M + 2 * D + 2, device=dev, dtype=torch.float32)
-    dchol = torch.empty(O, M, M, device=dev, dtype=torch.float32)
-    rc = lib.gpk_variational_chol_adjoint_batched_f32(
-        X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vmean.data_ptr(), vchol.data_ptr(),
-        hyper.data_ptr(), gmean.data_ptr(), gvar.data_ptr(), saved.detach().contiguous().data_ptr(), O, B, N, M,
-        D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(),
-        _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_adjoint_batched_f32")
-    return dX, dLinv, dZ, dpar, dchol
+    _multi_output(Z)
+    return _variational_chol_adjoint(X, Z, Linv, vmean, vchol, hyper, gmean, gvar, saved)
+
+
+def _cholesky_kl(m, chol, gkl=None):
+    """The KL (gkl None) or its gradient (dm, dchol) for m (M,), chol (M, M), or with a leading O."""
+    lead, M = tuple(m.shape[:-1]), m.shape[-1]
+    dev = m.device
+    if gkl is None:
+        kl = torch.empty(lead or (1,), device=dev, dtype=torch.float32)
+        outs = (kl.data_ptr(), None, None, None)
+    else:
+        dm, dchol = torch.empty_like(m), torch.empty_like(chol)
+        outs = (None, gkl.data_ptr(), dm.data_ptr(), dchol.data_ptr())
+    name = "gpk_cholesky_kl_batched_f32" if lead else "gpk_cholesky_kl_f32"
+    rc = getattr(_native.lib(), name)(m.data_ptr(), chol.data_ptr(), *lead, M, *outs, _stream_ptr(dev))
+    _native.check(rc, name)
+    return kl if gkl is None else (dm, dchol)
+
+
+def _kl_single(m: torch.Tensor) -> None:
+    if m.dim() != 1:
+        raise ValueError(f"m must be (M,), got {tuple(m.shape)}")
+
+
+def cholesky_kl(m: torch.Tensor, chol: torch.Tensor) -> torch.Tensor:
+    """KL(N(m, L L^T) || N(0, I)), L = tril(chol), as a (1,) tensor (one launch)."""
+    _require_device(m, chol)
+    _kl_single(m)
+    return _cholesky_kl(m, chol)
+
+
+def cholesky_kl_grad(m, chol, gkl):
+    _require_device(m, chol, gkl)
+    _kl_single(m)
+    return _cholesky_kl(m, chol, gkl)
 
 
 def _kl_batched_args(m, chol):
@@ -1616,59 +1477,19 @@ def _kl_batched_args(m, chol):
 def cholesky_kl_batched(m: torch.Tensor, chol: torch.Tensor) -> torch.Tensor:
     """KL(N(m_o, L_o L_o^T) || N(0, I)), L_o = tril(chol_o), per output as an (O,) tensor (one launch)."""
     _require_device(m, chol)
-    m, chol = _kl_batched_args(m, chol)
-    O, M = m.shape
-    kl = torch.empty(O, device=m.device, dtype=torch.float32)
-    rc = _native.lib().gpk_cholesky_kl_batched_f32(m.data_ptr(), chol.data_ptr(), O, M, kl.data_ptr(), None, None,
-                                                   None, _stream_ptr(m.device))
-    _native.check(rc, "gpk_cholesky_kl_batched_f32")
-    return kl
+    return _cholesky_kl(*_kl_batched_args(m, chol))
 
 
 def cholesky_kl_grad_batched(m, chol, gkl):
     _require_device(m, chol, gkl)
     m, chol = _kl_batched_args(m, chol)
-    O, M = m.shape
-    gkl = gkl.detach().reshape(O).contiguous().float()
-    dm = torch.empty_like(m)
-    dchol = torch.empty_like(chol)
-    rc = _native.lib().gpk_cholesky_kl_batched_f32(m.data_ptr(), chol.data_ptr(), O, M, None, gkl.data_ptr(),
-                                                   dm.data_ptr(), dchol.data_ptr(), _stream_ptr(m.device))
-    _native.check(rc, "gpk_cholesky_kl_batched_f32")
-    return dm, dchol
+    return _cholesky_kl(m, chol, gkl.detach().reshape(m.shape[0]).contiguous().float())
 
 
 # ---------------------------------------------------------------------------
 # Dense covariance of q(f) for a Cholesky q(u): gpk_variational_chol_cov_f32 / _grad_f32 and their
 # batched forms (Z (M, D): one output; Z (O, M, D): O outputs on one launch chain)
 # ---------------------------------------------------------------------------
-def _chol_cov_args(X, Z, Linv, vchol, hyper):
-    """Checked, contiguous arguments -> (X, shared, Z, Linv, vchol, hyper, O or None, B, N, M, D)."""
-    _require_device(X, Z, Linv, vchol, hyper)
-    if Z.dim() == 3:
-        O, M, D = Z.shape
-        X, shared = _batched_x(X, O)
-        lead = (O,)
-    elif Z.dim() == 2:
-        O, (M, D) = None, Z.shape
-        if X.dim() != 3:
-            raise ValueError(f"X must be (B, N, D), got {tuple(X.shape)}")
-        X, shared, lead = X.detach().contiguous().float(), True, ()
-    else:
-        raise ValueError(f"Z must be (M, D) or (O, M, D), got {tuple(Z.shape)}")
-    B, N = X.shape[-3], X.shape[-2]
-    if X.shape[-1] != D:
-        raise ValueError(f"Z must be (..., M, {X.shape[-1]}), got {tuple(Z.shape)}")
-    if tuple(Linv.shape) != lead + (M, M) or Linv.dtype != torch.float64:
-        raise ValueError(f"Linv must be {lead + (M, M)} float64 from kzz_cholesky")
-    if tuple(vchol.shape) != lead + (M, M):
-        raise ValueError(f"chol_variational_covar must be {lead + (M, M)}, got {tuple(vchol.shape)}")
-    if tuple(hyper.shape) != lead + (4 + 2 * D,):
-        raise ValueError(f"hyper must be {lead + (4 + 2 * D,)}, got {tuple(hyper.shape)}")
-    return (X, shared, Z.detach().contiguous().float(), Linv.detach().contiguous(),
-            vchol.detach().contiguous().float(), hyper.detach().contiguous().float(), O, B, N, M, D)
-
-
 def variational_chol_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, vchol: torch.Tensor,
                          hyper: torch.Tensor, return_state: bool = False):
     """Dense covariance of q(f) with a Cholesky q(u): K_XX + jitter I + W^T W - A^T A, A = Linv K_ZX,
@@ -1677,28 +1498,27 @@ def variational_chol_cov(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tensor, v
     with a leading O -> cov (O, B, N, N), output o bit-identical to a single-output call.
     ``return_state``: -> (cov, workspace), the stacked [W; A] panels and window means that
     ``variational_chol_cov_grad`` runs from (2 B M N floats, N rounded up to 64, per output)."""
-    X, shared, Z, Linv, vchol, hyper, O, B, N, M, D = _chol_cov_args(X, Z, Linv, vchol, hyper)
+    _require_device(X, Z, Linv, vchol, hyper)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
     dev = X.device
+    vchol = _vchol_arg(vchol, lead, M)
     lib = _native.lib()
     if O is None:
+        name = "gpk_variational_chol_cov_f32"
         nbytes = lib.gpk_variational_chol_cov_workspace_bytes(B, N, M)
     else:
+        name = "gpk_variational_chol_cov_batched_f32"
         nbytes = lib.gpk_variational_chol_cov_batched_workspace_bytes(O, B, N, M)
     if (nbytes == 0 and B > 0) or D > 64:
-        raise ValueError(f"gpk_variational_chol_cov_f32 does not support O={O}, B={B}, N={N}, M={M}, D={D}")
-    cov = torch.empty(*(() if O is None else (O,)), B, N, N, device=dev, dtype=torch.float32)
+        raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+    cov = torch.empty(*lead, B, N, N, device=dev, dtype=torch.float32)
     if B == 0:
         return (cov, torch.empty(0, device=dev, dtype=torch.float32)) if return_state else cov
     ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
-    if O is None:
-        rc = lib.gpk_variational_chol_cov_f32(X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(),
-                                              hyper.data_ptr(), B, N, M, D, ws.data_ptr(), cov.data_ptr(),
-                                              _stream_ptr(dev))
-    else:
-        rc = lib.gpk_variational_chol_cov_batched_f32(
-            X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(), O, B,
-            N, M, D, ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_cov_f32")
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(), *dims,
+                            ws.data_ptr(), cov.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
     return (cov, ws) if return_state else cov
 
 
@@ -1709,22 +1529,24 @@ def variational_chol_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tens
     (dX, dLinv float64 lower, dZ (the K_ZX part), dpar = [ds2, dlengthscale (D)], dchol lower).
     Z (O, M, D): every array with a leading O, dX (O, B, N, D) per output also with shared inputs
     (the caller sums over O). M <= 256, D <= 64, N <= 256."""
-    X, shared, Z, Linv, vchol, hyper, O, B, N, M, D = _chol_cov_args(X, Z, Linv, vchol, hyper)
-    _require_device(state, gcov)
+    _require_device(X, Z, Linv, vchol, hyper, state, gcov)
+    X, shared, Z, Linv, hyper, lead, O, B, N, M, D = _var_args(X, Z, Linv, hyper)
     dev = X.device
-    lead = () if O is None else (O,)
+    vchol = _vchol_arg(vchol, lead, M)
     if tuple(gcov.shape) != lead + (B, N, N):
         raise ValueError(f"gcov must be {lead + (B, N, N)}, got {tuple(gcov.shape)}")
     gcov = gcov.detach().contiguous().float()
     lib = _native.lib()
     if O is None:
+        name = "gpk_variational_chol_cov_grad_f32"
         nbytes = lib.gpk_variational_chol_cov_grad_workspace_bytes(B, N, M, D)
         nstate = lib.gpk_variational_chol_cov_workspace_bytes(B, N, M)
     else:
+        name = "gpk_variational_chol_cov_grad_batched_f32"
         nbytes = lib.gpk_variational_chol_cov_grad_batched_workspace_bytes(O, B, N, M, D)
         nstate = lib.gpk_variational_chol_cov_batched_workspace_bytes(O, B, N, M)
     if nbytes == 0 and B > 0:
-        raise ValueError(f"gpk_variational_chol_cov_grad_f32 does not support O={O}, B={B}, N={N}, M={M}, D={D}")
+        raise ValueError(f"{name} does not support O={O}, B={B}, N={N}, M={M}, D={D}")
     dX = torch.empty(*lead, B, N, D, device=dev, dtype=torch.float32)
     dLinv = torch.empty(*lead, M, M, device=dev, dtype=torch.float64)
     dZ = torch.empty(*lead, M, D, device=dev, dtype=torch.float32)
@@ -1732,20 +1554,11 @@ def variational_chol_cov_grad(X: torch.Tensor, Z: torch.Tensor, Linv: torch.Tens
     dchol = torch.empty(*lead, M, M, device=dev, dtype=torch.float32)
     if B == 0:
         return dX, dLinv.zero_(), dZ.zero_(), dpar.zero_(), dchol.zero_()
-    if state.dtype != torch.float32 or state.device != dev or state.numel() != max(1, nstate // 4):
-        raise ValueError(f"state must be the {nstate // 4} float32 values on {dev} that "
-                         f"variational_chol_cov(return_state=True) returned for this shape")
-    state = state.detach().contiguous()
+    state = _cov_grad_state(state, nstate // 4, dev, "variational_chol_cov")
     ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-    if O is None:
-        rc = lib.gpk_variational_chol_cov_grad_f32(
-            X.data_ptr(), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(), state.data_ptr(),
-            gcov.data_ptr(), B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(), dZ.data_ptr(),
-            dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
-    else:
-        rc = lib.gpk_variational_chol_cov_grad_batched_f32(
-            X.data_ptr(), int(shared), Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
-            state.data_ptr(), gcov.data_ptr(), O, B, N, M, D, ws.data_ptr(), dX.data_ptr(), dLinv.data_ptr(),
-            dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
-    _native.check(rc, "gpk_variational_chol_cov_grad_f32")
+    x, dims = _abi(X, shared, O, B, N, M, D)
+    rc = getattr(lib, name)(*x, Z.data_ptr(), Linv.data_ptr(), vchol.data_ptr(), hyper.data_ptr(),
+                            state.data_ptr(), gcov.data_ptr(), *dims, ws.data_ptr(), dX.data_ptr(),
+                            dLinv.data_ptr(), dZ.data_ptr(), dpar.data_ptr(), dchol.data_ptr(), _stream_ptr(dev))
+    _native.check(rc, name)
     return dX, dLinv, dZ, dpar, dchol

@@ -82,10 +82,8 @@ class KzzCache:
         e = self._entry
         if e is not None and e["key"] == key and e["grad"] == grad and not e["spent"]:
             return e["Linv"]
-        if Z.dim() == 3:     # a multi-output layer: the O factors in one entry, one launch chain
-            Linv, _, info = torch.ops.gpk.kzz_factor_batched(Z, s2, ls, float(jitter), 1e-8, 3)
-        else:
-            Linv, _, info = torch.ops.gpk.kzz_factor(Z, s2, ls, float(jitter), 1e-8, 3)
+        # Z (O, M, D), a multi-output layer: the O factors in one entry, one launch chain
+        Linv, _, info = torch.ops.gpk.kzz_factor(Z, s2, ls, float(jitter), 1e-8, 3)
         entry = {"key": key, "grad": grad, "Linv": Linv, "spent": False, "info": info, "Z": Z}
         if grad:
             def _spent(g, entry=entry):
@@ -136,60 +134,6 @@ def _mean_params(mean_module, D, device):
                               "(DeepGP.py:42-45: ConstantMean or LinearMean)")
 
 
-def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
-                        cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False,
-                        return_hyper: bool = False):
-    """q(f) mean / variance / clamp flag for (B, N, D) windows (HIP forward and backward;
-    see module docstring). ``cache`` shares the K_ZZ factor between calls; ``return_linv``
-    appends the factor's L^{-1} (for a lazily materialised covariance), ``return_hyper`` the
-    packed hyper vector of the forward (what gpk::variational_cov reads)."""
-    w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
-    s2 = outputscale.reshape(())
-    ls = lengthscale.reshape(-1)
-    if cache is None or key_tensors is None:
-        # no caller-held parameters to key on: a fresh, private factor (keys on derived
-        # temporaries could alias reused allocator memory and return a stale factor)
-        cache = KzzCache()
-        key_tensors = (Z, s2, ls)
-    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
-    # training (a gradient will flow): the forward keeps A for the saved-state adjoint
-    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
-    mean, var, flags, hyper, _ = torch.ops.gpk.variational_fwd(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
-                                                               float(jitter), save)
-    cache.note_consumers(mean, var)
-    cache.check_pending()
-    out = (mean, var, flags)
-    if return_linv:
-        out += (Linv,)
-    if return_hyper:
-        out += (hyper,)
-    return out
-
-
-def variational_predict_chol(x, Z, vmean, vchol, outputscale, lengthscale, mean_module, jitter,
-                             cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
-    """``variational_predict`` for a Cholesky q(u) = N(vmean, L_q L_q^T), L_q = tril(vchol)
-    (gpk::variational_chol_fwd, HIP forward and backward): the same shared K_ZZ factor, spent-marking
-    and pending psd_safe_cholesky verdict. The caller has checked that the kernels serve the shape
-    (ops.variational_chol_supported)."""
-    w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
-    s2 = outputscale.reshape(())
-    ls = lengthscale.reshape(-1)
-    if cache is None or key_tensors is None:
-        cache = KzzCache()
-        key_tensors = (Z, s2, ls)
-    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
-    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vchol, s2, ls, w, b0))
-    mean, var, flags, _, _ = torch.ops.gpk.variational_chol_fwd(x, Linv, Z, vmean, vchol, s2, ls, w, b0,
-                                                                float(jitter), save)
-    cache.note_consumers(mean, var)
-    cache.check_pending()
-    out = (mean, var, flags)
-    if return_linv:
-        out += (Linv,)
-    return out
-
-
 def _mean_params_batched(mean_module, O, D, device):
     """(w, b0) of a multi-output layer's mean (DeepGP.py:42-45): ConstantMean(batch_shape=[O])
     as w = 0, b0 (O,) (one gradient per output); LinearMean with weights (O, D, 1) per output,
@@ -209,6 +153,52 @@ def _mean_params_batched(mean_module, O, D, device):
                               "(DeepGP.py:42-45: ConstantMean or LinearMean)")
 
 
+def _predict(fwd, x, Z, q, s2, ls, w, b0, jitter, cache, key_tensors, return_linv, return_hyper):
+    """The sequence every ``variational_predict*`` runs once its arguments have their shapes: the
+    shared K_ZZ factor from ``cache``, the forward op ``fwd`` on the q(u) parameters ``q``, the
+    spent-marking of the factor and its pending psd_safe_cholesky verdict."""
+    if cache is None or key_tensors is None:
+        # no caller-held parameters to key on: a fresh, private factor (keys on derived
+        # temporaries could alias reused allocator memory and return a stale factor)
+        cache = KzzCache()
+        key_tensors = (Z, s2, ls)
+    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
+    # training (a gradient will flow): the forward keeps A for the saved-state adjoint
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, *q, s2, ls, w, b0))
+    mean, var, flags, hyper, _ = fwd(x, Linv, Z, *q, s2, ls, w, b0, float(jitter), save)
+    cache.note_consumers(mean, var)
+    cache.check_pending()
+    out = (mean, var, flags)
+    if return_linv:
+        out += (Linv,)
+    if return_hyper:
+        out += (hyper,)
+    return out
+
+
+def variational_predict(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
+                        cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False,
+                        return_hyper: bool = False):
+    """q(f) mean / variance / clamp flag for (B, N, D) windows (HIP forward and backward;
+    see module docstring). ``cache`` shares the K_ZZ factor between calls; ``return_linv``
+    appends the factor's L^{-1} (for a lazily materialised covariance), ``return_hyper`` the
+    packed hyper vector of the forward (what gpk::variational_cov reads)."""
+    w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
+    return _predict(torch.ops.gpk.variational_fwd, x, Z, (vmean, vstd), outputscale.reshape(()),
+                    lengthscale.reshape(-1), w, b0, jitter, cache, key_tensors, return_linv, return_hyper)
+
+
+def variational_predict_chol(x, Z, vmean, vchol, outputscale, lengthscale, mean_module, jitter,
+                             cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False):
+    """``variational_predict`` for a Cholesky q(u) = N(vmean, L_q L_q^T), L_q = tril(vchol)
+    (gpk::variational_chol_fwd, HIP forward and backward): the same shared K_ZZ factor, spent-marking
+    and pending psd_safe_cholesky verdict. The caller has checked that the kernels serve the shape
+    (ops.variational_chol_supported)."""
+    w, b0 = _mean_params(mean_module, x.shape[-1], x.device)
+    return _predict(torch.ops.gpk.variational_chol_fwd, x, Z, (vmean, vchol), outputscale.reshape(()),
+                    lengthscale.reshape(-1), w, b0, jitter, cache, key_tensors, return_linv, False)
+
+
 def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mean_module, jitter,
                                 cache: Optional[KzzCache] = None, key_tensors=None, return_linv: bool = False,
                                 return_hyper: bool = False):
@@ -220,52 +210,22 @@ def variational_predict_batched(x, Z, vmean, vstd, outputscale, lengthscale, mea
     single output."""
     O, _, D = Z.shape
     w, b0 = _mean_params_batched(mean_module, O, D, x.device)
-    s2 = outputscale.reshape(O)
-    ls = lengthscale.reshape(O, -1)
-    vmean = vmean.reshape(O, -1)
-    vstd = vstd.reshape(O, -1)
-    if cache is None or key_tensors is None:
-        cache = KzzCache()
-        key_tensors = (Z, s2, ls)
-    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
-    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vstd, s2, ls, w, b0))
-    mean, var, flags, hyper, _ = torch.ops.gpk.variational_fwd_batched(x, Linv, Z, vmean, vstd, s2, ls, w, b0,
-                                                                       float(jitter), save)
-    cache.note_consumers(mean, var)
-    cache.check_pending()
-    out = (mean, var, flags)
-    if return_linv:
-        out += (Linv,)
-    if return_hyper:
-        out += (hyper,)
-    return out
+    return _predict(torch.ops.gpk.variational_fwd, x, Z, (vmean.reshape(O, -1), vstd.reshape(O, -1)),
+                    outputscale.reshape(O), lengthscale.reshape(O, -1), w, b0, jitter, cache, key_tensors,
+                    return_linv, return_hyper)
 
 
 def variational_predict_chol_batched(x, Z, vmean, vchol, outputscale, lengthscale, mean_module, jitter,
                                      cache: Optional[KzzCache] = None, key_tensors=None,
                                      return_linv: bool = False):
     """``variational_predict_batched`` for a Cholesky q(u) per output, N(vmean_o, L_o L_o^T) with
-    L_o = tril(vchol_o) (gpk::variational_chol_fwd_batched, one launch chain each way): x (B, N, D)
+    L_o = tril(vchol_o) (gpk::variational_chol_fwd, one launch chain each way): x (B, N, D)
     shared by the outputs or (O, B, N, D), Z (O, M, D), vmean (O, M), vchol (O, M, M) -> mean, var
     (O, B, N), one clamp flag for all outputs (and Linv (O, M, M)). The same ``KzzCache`` entry for
     the (O, M, M) factor, spent-marking and pending verdict as the mean-field sibling. The caller
     has checked that the kernels serve the shape (ops.variational_chol_batched_supported)."""
     O, M, D = Z.shape
     w, b0 = _mean_params_batched(mean_module, O, D, x.device)
-    s2 = outputscale.reshape(O)
-    ls = lengthscale.reshape(O, -1)
-    vmean = vmean.reshape(O, M)
-    vchol = vchol.reshape(O, M, M)
-    if cache is None or key_tensors is None:
-        cache = KzzCache()
-        key_tensors = (Z, s2, ls)
-    Linv = cache.factor(Z, s2, ls, jitter, key_tensors)
-    save = torch.is_grad_enabled() and any(t.requires_grad for t in (x, Linv, Z, vmean, vchol, s2, ls, w, b0))
-    mean, var, flags, _, _ = torch.ops.gpk.variational_chol_fwd_batched(x, Linv, Z, vmean, vchol, s2, ls, w, b0,
-                                                                        float(jitter), save)
-    cache.note_consumers(mean, var)
-    cache.check_pending()
-    out = (mean, var, flags)
-    if return_linv:
-        out += (Linv,)
-    return out
+    return _predict(torch.ops.gpk.variational_chol_fwd, x, Z, (vmean.reshape(O, M), vchol.reshape(O, M, M)),
+                    outputscale.reshape(O), lengthscale.reshape(O, -1), w, b0, jitter, cache, key_tensors,
+                    return_linv, False)

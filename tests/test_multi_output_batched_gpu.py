@@ -420,21 +420,21 @@ def test_batched_custom_ops_opcheck(cuda_device):
     Z = (torch.randn(no, M, D, generator=g) / 2).to(dev)
     s2 = torch.tensor([0.8, 0.6], device=dev)
     ls = torch.full((no, D), 0.7, device=dev)
-    torch.library.opcheck(torch.ops.gpk.kzz_factor_batched.default, (Z, s2, ls, 1e-4, 1e-8, 3), test_utils=tests)
-    Linv = torch.ops.gpk.kzz_factor_batched(Z, s2, ls, 1e-4, 1e-8, 3)[0]
+    torch.library.opcheck(torch.ops.gpk.kzz_factor.default, (Z, s2, ls, 1e-4, 1e-8, 3), test_utils=tests)
+    Linv = torch.ops.gpk.kzz_factor(Z, s2, ls, 1e-4, 1e-8, 3)[0]
     vm = (1e-3 * torch.randn(no, M, generator=g)).to(dev)
     args = (X, Linv, Z, vm, torch.ones(no, M, device=dev), s2, ls, torch.randn(D, generator=g).to(dev),
             torch.tensor([0.1], device=dev), 1e-4)
-    torch.library.opcheck(torch.ops.gpk.variational_fwd_batched.default, args, test_utils=tests)
-    mean, var, _, hyp, saved = torch.ops.gpk.variational_fwd_batched(*args)
+    torch.library.opcheck(torch.ops.gpk.variational_fwd.default, args, test_utils=tests)
+    mean, var, _, hyp, saved = torch.ops.gpk.variational_fwd(*args)
     adj_args = (X, Linv, Z, vm, args[4], hyp, torch.randn_like(mean), torch.randn_like(var), saved)
-    torch.library.opcheck(torch.ops.gpk.variational_adj_batched.default, adj_args, test_utils=tests)
+    torch.library.opcheck(torch.ops.gpk.variational_adj.default, adj_args, test_utils=tests)
     # with gradients requested, the registered autograd formulas are exercised
     Zr = Z.clone().requires_grad_(True)
-    torch.library.opcheck(torch.ops.gpk.kzz_factor_batched.default, (Zr, s2, ls, 1e-4, 1e-8, 3),
+    torch.library.opcheck(torch.ops.gpk.kzz_factor.default, (Zr, s2, ls, 1e-4, 1e-8, 3),
                           test_utils=("test_autograd_registration",))
     Xr = X.clone().requires_grad_(True)
-    torch.library.opcheck(torch.ops.gpk.variational_fwd_batched.default, (Xr,) + args[1:],
+    torch.library.opcheck(torch.ops.gpk.variational_fwd.default, (Xr,) + args[1:],
                           test_utils=("test_autograd_registration",))
 
 

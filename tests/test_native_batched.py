@@ -122,7 +122,7 @@ def test_batched_ops_refuse_cpu_tensors_and_bad_shapes():
 def test_batched_custom_ops_fake_shapes():
     import fine_grained_gaussian_process_forcasting_amd.library  # noqa: F401
     from torch._subclasses.fake_tensor import FakeTensorMode
-    for n in ("kzz_factor_batched", "variational_fwd_batched", "variational_adj_batched"):
+    for n in ("kzz_factor", "variational_fwd", "variational_adj"):
         assert hasattr(torch.ops.gpk, n), n
     nat = _lib().gpk_variational_saved_bytes(3, 16, 256, 4) // 4
     assert nat == 3 * 1 * (16 * 2 * 256 + 32)
@@ -130,28 +130,28 @@ def test_batched_custom_ops_fake_shapes():
         O, B, N, M, D = 3, 3, 16, 8, 4
         X = torch.empty(B, N, D)
         Z = torch.empty(O, M, D)
-        Linv, L, info = torch.ops.gpk.kzz_factor_batched(Z, torch.empty(O), torch.empty(O, D), 1e-4, 1e-8, 3)
+        Linv, L, info = torch.ops.gpk.kzz_factor(Z, torch.empty(O), torch.empty(O, D), 1e-4, 1e-8, 3)
         assert Linv.shape == (O, M, M) and Linv.dtype == torch.float64 and L.shape == (O, M, M)
         assert info.shape == (O,) and info.dtype == torch.int32
-        mean, var, flags, hyp, saved = torch.ops.gpk.variational_fwd_batched(
+        mean, var, flags, hyp, saved = torch.ops.gpk.variational_fwd(
             X, Linv, Z, torch.empty(O, M), torch.empty(O, M), torch.empty(O), torch.empty(O, D), torch.empty(D),
             torch.empty(1), 1e-4)
         assert mean.shape == (O, B, N) and var.shape == (O, B, N) and mean.dtype == torch.float32
         assert flags.shape == (1,) and flags.dtype == torch.int32
         assert hyp.shape == (O, 4 + 2 * D) and saved.numel() == 0
         # per-output inputs and a per-output mean
-        mean4 = torch.ops.gpk.variational_fwd_batched(
+        mean4 = torch.ops.gpk.variational_fwd(
             torch.empty(O, B, N, D), Linv, Z, torch.empty(O, M), torch.empty(O, M), torch.empty(O),
             torch.empty(O, D), torch.empty(O, D), torch.empty(O), 1e-4)[0]
         assert mean4.shape == (O, B, N)
         # training at M = 256: O x the native saved-state size
         Z2 = torch.empty(O, 256, D)
         L2 = torch.empty(O, 256, 256, dtype=torch.float64)
-        out = torch.ops.gpk.variational_fwd_batched(X, L2, Z2, torch.empty(O, 256), torch.empty(O, 256),
+        out = torch.ops.gpk.variational_fwd(X, L2, Z2, torch.empty(O, 256), torch.empty(O, 256),
                                                     torch.empty(O), torch.empty(O, D), torch.empty(D),
                                                     torch.empty(1), 1e-4, True)
         assert out[4].numel() == O * nat and out[4].dtype == torch.float32
-        dX, dL, dZ, dpar = torch.ops.gpk.variational_adj_batched(X, L2, Z2, torch.empty(O, 256),
+        dX, dL, dZ, dpar = torch.ops.gpk.variational_adj(X, L2, Z2, torch.empty(O, 256),
                                                                  torch.empty(O, 256), out[3], out[0], out[1],
                                                                  out[4])
         assert dX.shape == (O, B, N, D) and dL.shape == (O, 256, 256) and dL.dtype == torch.float64

@@ -239,7 +239,7 @@ def test_cholesky_kl_batched(cuda_device, O, M):
     gk = torch.tensor([2.5 - 0.75 * o for o in range(O)])
     m = m0.to(dev).requires_grad_(True)
     C = C0.to(dev).requires_grad_(True)
-    got = torch.ops.gpk.cholesky_kl_batched(m, C)
+    got = torch.ops.gpk.cholesky_kl(m, C)
     assert got.shape == (O,)
     (gk.to(dev) * got).sum().backward()
     got = got.detach()
@@ -296,7 +296,7 @@ def test_layer_matches_the_torch_fallback(cuda_device, monkeypatch, mean_type):
     gv = torch.randn(1, 4, 30, O, generator=g).to(dev)
     predicts, closed, factors = [], [], []
     real_predict, real_closed = gp.variational_chol_predict, gp.cholesky_kl_closed_form
-    real_factor = torch.ops.gpk.kzz_factor_batched
+    real_factor = torch.ops.gpk.kzz_factor
     monkeypatch.setattr(gp, "variational_chol_predict", lambda *a: (predicts.append(1), real_predict(*a))[1])
     monkeypatch.setattr(gp, "cholesky_kl_closed_form", lambda *a: (closed.append(1), real_closed(*a))[1])
 
@@ -312,7 +312,7 @@ def test_layer_matches_the_torch_fallback(cuda_device, monkeypatch, mean_type):
         layer = _chol_layer(D, 7, M, dev, O, mean_type)
         x = x0.clone().requires_grad_(True)
         with monkeypatch.context() as mp:
-            mp.setattr(torch.ops.gpk, "kzz_factor_batched", _Counted())
+            mp.setattr(torch.ops.gpk, "kzz_factor", _Counted())
             if fallback:
                 mp.setattr(ops, "variational_chol_batched_supported", lambda *a, **k: False)
             with settings.num_likelihood_samples(1):
@@ -349,24 +349,24 @@ def test_ops_opcheck(cuda_device):
     O, B, N, M, D = 2, 2, 24, 8, 4
     d = _stacked(dev, True, O, B, N, M, D)
     tests = ("test_schema", "test_autograd_registration", "test_faketensor")
-    Linv = torch.ops.gpk.kzz_factor_batched(d["Z"], d["s2"], d["ls"], JIT, 1e-8, 3)[0]
+    Linv = torch.ops.gpk.kzz_factor(d["Z"], d["s2"], d["ls"], JIT, 1e-8, 3)[0]
     for X in (d["X"], d["X"].expand(O, B, N, D).contiguous()):
         args = (X, Linv, d["Z"], d["m"], d["C"], d["s2"], d["ls"], d["w"], d["b0"], JIT)
-        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd_batched.default, args, test_utils=tests)
-        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd_batched.default, args + (True,), test_utils=tests)
+        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd.default, args, test_utils=tests)
+        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd.default, args + (True,), test_utils=tests)
         # with gradients requested the registered autograd formula runs
         req = tuple(t.clone().requires_grad_(True) if torch.is_tensor(t) and t.is_floating_point() else t
                     for t in args)
-        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd_batched.default, req + (True,),
+        torch.library.opcheck(torch.ops.gpk.variational_chol_fwd.default, req + (True,),
                               test_utils=tests)
-    mean, var, _, hyp, saved = torch.ops.gpk.variational_chol_fwd_batched(*args, True)
+    mean, var, _, hyp, saved = torch.ops.gpk.variational_chol_fwd(*args, True)
     assert saved.numel() == O * (B * M * 64 + B * 64)
-    torch.library.opcheck(torch.ops.gpk.variational_chol_adj_batched.default,
+    torch.library.opcheck(torch.ops.gpk.variational_chol_adj.default,
                           (X, Linv, d["Z"], d["m"], d["C"], hyp, d["gmean"], d["gvar"], saved),
                           test_utils=("test_schema", "test_faketensor"))
-    torch.library.opcheck(torch.ops.gpk.cholesky_kl_batched.default,
+    torch.library.opcheck(torch.ops.gpk.cholesky_kl.default,
                           (d["m"].clone().requires_grad_(True), d["C"].clone().requires_grad_(True)),
                           test_utils=tests)
-    torch.library.opcheck(torch.ops.gpk.cholesky_kl_grad_batched.default,
+    torch.library.opcheck(torch.ops.gpk.cholesky_kl_grad.default,
                           (d["m"], d["C"], torch.tensor([1.5, -0.5], device=dev)),
                           test_utils=("test_schema", "test_faketensor"))

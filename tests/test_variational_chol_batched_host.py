@@ -53,27 +53,26 @@ def test_new_symbols_bound_and_ops_registered():
               "cholesky_kl_grad_batched", "variational_chol_batched_supported"):
         assert hasattr(ops, n), n
     assert hasattr(ops_autograd, "variational_predict_chol_batched")
-    for n in ("variational_chol_fwd_batched", "variational_chol_adj_batched", "cholesky_kl_batched",
-              "cholesky_kl_grad_batched"):
+    for n in ("variational_chol_fwd", "variational_chol_adj", "cholesky_kl", "cholesky_kl_grad"):
         assert hasattr(torch.ops.gpk, n), n
     with FakeTensorMode():
         O, B, N, M, D = 3, 2, 70, 20, 4
         Z, Linv = torch.empty(O, M, D), torch.empty(O, M, M, dtype=torch.float64)
         vm, vc = torch.empty(O, M), torch.empty(O, M, M)
         for X in (torch.empty(B, N, D), torch.empty(O, B, N, D)):
-            mean, var, flags, hyp, saved = torch.ops.gpk.variational_chol_fwd_batched(
+            mean, var, flags, hyp, saved = torch.ops.gpk.variational_chol_fwd(
                 X, Linv, Z, vm, vc, torch.empty(O), torch.empty(O, D), torch.empty(D), torch.empty(1), 1e-4, True)
             assert mean.shape == (O, B, N) and var.shape == (O, B, N) and flags.dtype == torch.int32
             assert hyp.shape == (O, 4 + 2 * D) and saved.numel() == O * (B * M * 128 + B * 128)
-            dX, dL, dZ, dpar, dC = torch.ops.gpk.variational_chol_adj_batched(X, Linv, Z, vm, vc, hyp, mean, var,
+            dX, dL, dZ, dpar, dC = torch.ops.gpk.variational_chol_adj(X, Linv, Z, vm, vc, hyp, mean, var,
                                                                               saved)
             assert dX.shape == (O, B, N, D) and dL.shape == (O, M, M) and dL.dtype == torch.float64
             assert dZ.shape == (O, M, D) and dpar.shape == (O, M + 2 * D + 2) and dC.shape == (O, M, M)
-        out = torch.ops.gpk.variational_chol_fwd_batched(X, Linv, Z, vm, vc, torch.empty(O), torch.empty(O, D),
+        out = torch.ops.gpk.variational_chol_fwd(X, Linv, Z, vm, vc, torch.empty(O), torch.empty(O, D),
                                                          torch.empty(D), torch.empty(1), 1e-4)
         assert out[4].numel() == 0
-        assert torch.ops.gpk.cholesky_kl_batched(vm, vc).shape == (O,)
-        dm, dC = torch.ops.gpk.cholesky_kl_grad_batched(vm, vc, torch.empty(O))
+        assert torch.ops.gpk.cholesky_kl(vm, vc).shape == (O,)
+        dm, dC = torch.ops.gpk.cholesky_kl_grad(vm, vc, torch.empty(O))
         assert dm.shape == (O, M) and dC.shape == (O, M, M)
 
 
