@@ -13,6 +13,10 @@
 size_t gpk_mvn_root_refine_ws_floats(int B, int n);
 int gpk_launch_mvn_root_refine(const float* cov, const float* R, int B, int n, float jitter, float* ws,
                                float* Rout, hipStream_t stream);
+size_t gpk_exact_append_ws_floats(int B, int N, int m);
+int gpk_launch_exact_append(const float* X, const float* L, const float* z, const float* hyp, int n_ls,
+                            long long hyp_stride, const float* Xn, const float* yn, int B, int N, int m, int D,
+                            float jitter, float* ws, float* Lout, float* zout, int* info, hipStream_t stream);
 
 extern "C" {
 
@@ -182,6 +186,47 @@ int gpk_exact_posterior_cov_f32(const float* X, const float* L, const float* z, 
                                 void* workspace, float* mean, float* var, float* cov, void* stream) {
   return gpk_exact_posterior_cov_perwin_f32(X, L, z, hyp, n_lengthscale, 0, Xs, B, N, Ns, D, workspace, mean, var,
                                             cov, stream);
+}
+
+// ---- appending observations to a cached factor (gpk_exact_append.hip)
+size_t gpk_exact_append_workspace_bytes(int B, int N, int m) {
+  if (B < 0 || N < 1 || m < 1 || m > kGpkMvnRootMaxN || N + m > gpk_exact_max_n()) return 0;
+  if (N > kGpkExactRegMaxN && B > 65535) return 0;
+  return gpk_exact_append_ws_floats(B, N, m) * sizeof(float);
+}
+
+int gpk_exact_append_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                int n_lengthscale, long long hyp_stride, const float* Xn, const float* yn,
+                                int B, int N, int m, int D, float jitter, void* workspace, float* Lout,
+                                float* zout, int* info, void* stream) {
+  if (X == nullptr) return -1;
+  if (L == nullptr) return -2;
+  if (z == nullptr) return -3;
+  if (hyp == nullptr) return -4;
+  if (n_lengthscale != 1 && n_lengthscale != D) return -5;
+  if (!hyp_stride_ok(hyp_stride, n_lengthscale)) return -6;
+  if (Xn == nullptr) return -6;
+  if (yn == nullptr) return -7;
+  if (B < 0) return -8;
+  if (N < 1 || N > gpk_exact_max_n()) return -9;
+  if (m < 1 || m > kGpkMvnRootMaxN || N + m > gpk_exact_max_n()) return -10;
+  if (D < 1 || D > 64) return -11;
+  if (!(jitter >= 0.f)) return -12;
+  if (B > 0 && (workspace == nullptr || ((size_t)workspace & 15) != 0)) return -13;   // V rows are read 16 B at a time
+  if (Lout == nullptr) return -14;
+  if (zout == nullptr) return -15;
+  if (info == nullptr) return -16;
+  if (B == 0) return 0;
+  if (N > kGpkExactRegMaxN && B > 65535) return -8;   // the blocked phase 1 keeps B on gridDim.y
+  return gpk_launch_exact_append(X, L, z, hyp, n_lengthscale, hyp_stride, Xn, yn, B, N, m, D, jitter,
+                                 (float*)workspace, Lout, zout, info, (hipStream_t)stream);
+}
+
+int gpk_exact_append_f32(const float* X, const float* L, const float* z, const float* hyp, int n_lengthscale,
+                         const float* Xn, const float* yn, int B, int N, int m, int D, float jitter,
+                         void* workspace, float* Lout, float* zout, int* info, void* stream) {
+  return gpk_exact_append_perwin_f32(X, L, z, hyp, n_lengthscale, 0, Xn, yn, B, N, m, D, jitter, workspace, Lout,
+                                     zout, info, stream);
 }
 
 // ---- adjoint of the exact posterior (gpk_posterior_grad.hip)

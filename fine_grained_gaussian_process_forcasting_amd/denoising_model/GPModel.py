@@ -20,6 +20,10 @@ differentiable torch restatement of ``_posterior_autograd``).
 calling the model in eval mode on the training inputs warns (GPInputWarning) and
 returns the posterior there.
 
+``model.get_fantasy_model(new_x, new_y)`` conditions a model that has predicted on later
+observations without fitting again: gpk_exact_append_f32 extends the cached factor by the new
+points and the returned model starts with that cache.
+
 Inputs may be batched (B, N, D) windows, a single (N, D) window or 1-D (N,) points,
 as GPyTorch accepts; targets follow (B, N) / (N,).
 
@@ -34,6 +38,7 @@ other way round) is a mixed model and works the same way.
 """
 from __future__ import annotations
 
+import copy
 import warnings
 import weakref
 
@@ -122,6 +127,97 @@ class ExactGPModel(nn.Module):
     def train(self, mode: bool = True):
         self._prediction_cache = None       # GPyTorch drops its prediction strategy here
         return super().train(mode)
+
+    def get_fantasy_model(self, inputs, targets, **kwargs):
+        """A new model conditioned on the training data plus the observations (inputs, targets),
+        without fitting again (upstream models/exact_gp.py ExactGP.get_fantasy_model): the cached
+        training factor L and z = L^{-1}(y - c) are extended by the m new points in O(N^2 m) with
+        one gpk::exact_append call (include/gpk.h::gpk_exact_append_f32) and seed the new model's
+        prediction cache, so its first ``model(x)`` under ``no_grad`` launches no factorisation.
+        Up to N + m = 256 the cache is seeded by the fused forward on the concatenated data instead,
+        which is faster there than the update's launch chain.
+
+        ``inputs`` is (m,), (m, D) or (B, m, D) (or a list / tuple of one such tensor), ``targets``
+        (m,) or (B, m); an unbatched one is expanded to every window. The model must have been
+        called in eval mode since the last ``train()`` / ``set_train_data`` (the test-independent
+        caches must exist); otherwise RuntimeError, in upstream's words (GPyTorch 1.9 as
+        remembered, unpinned). Upstream's batch of fantasies (``targets`` with one more leading
+        dimension than the inputs) and the ``noise=`` keyword of FixedNoiseGaussianLikelihood
+        raise NotImplementedError.
+
+        Returns a deep copy of the modules (parameters included; the training data and the cached
+        factor are taken off before the copy) with the concatenated ``train_inputs`` /
+        ``train_targets``; this model and its cache are left untouched, and fantasies chain.
+        With gradients the new model behaves as any model with that training data (the eval path
+        under grad refits from the live parameters). More than 256 new points at once
+        (gpk_mvn_root_max_n) give the new model without a seeded cache: its first eval call
+        factors from scratch. The Schur complement's factorisation runs psd_safe_cholesky's jitter
+        ladder (NumericalWarning per retry, NanError, NotPSDError)."""
+        if kwargs.get("noise") is not None:
+            raise NotImplementedError("get_fantasy_model(noise=...) belongs to FixedNoiseGaussianLikelihood, "
+                                      "which this package does not have")
+        x = inputs[0] if isinstance(inputs, (tuple, list)) else inputs
+        xn = _as_batch(x)
+        lead = 0 if x.dim() < 3 else 1                 # batch dimensions of the inputs
+        if targets.dim() == lead + 2:
+            raise NotImplementedError("a batch of fantasies (targets with one more leading dimension than the "
+                                      "inputs) is not supported: add one set of observations per window")
+        if targets.dim() != lead + 1 and not (lead == 1 and targets.dim() == 1):
+            raise ValueError(f"targets must be (m,) or (B, m), got {tuple(targets.shape)}")
+        if self._prediction_cache is None:
+            raise RuntimeError("Fantasy observations can only be added after making predictions with a model so "
+                               "that all test independent caches exist. Call the model on some data first!")
+        self._check_windows(x)
+        train_x, train_y = self.train_inputs[0], self.train_targets
+        Xb, L, z, hyper = self._train_factor()         # the cache, or a refit if it went stale
+        B, N, D = Xb.shape
+        if xn.shape[-1] != D or xn.shape[0] not in (1, B):
+            raise ValueError(f"inputs of shape {tuple(x.shape)} do not match the training inputs "
+                             f"{tuple(train_x.shape)}")
+        m = xn.shape[1]
+        xn = xn.expand(B, m, D)
+        if targets.shape[-1] != m or (targets.dim() == 2 and targets.shape[0] != B):
+            raise ValueError(f"targets of shape {tuple(targets.shape)} do not match {m} new point(s) in {B} "
+                             "window(s)")
+        yn = targets.expand(B, m) if targets.dim() == 1 else targets
+        from .. import _native
+        if N + m > _native.lib().gpk_exact_max_n():
+            _native.check(-6, ops._exact_name("mll", hyper.dim() - 1))    # what ops.exact_mll raises for N + m
+
+        new_x = torch.cat([_as_batch(train_x), xn.to(train_x.dtype)], dim=1)
+        new_x = new_x.reshape(-1) if train_x.dim() == 1 else (new_x.squeeze(0) if train_x.dim() == 2 else new_x)
+        new_y = torch.cat([train_y.reshape(B, N), yn.to(train_y.dtype)], dim=1)
+        new_y = new_y.reshape(-1) if train_y.dim() == 1 else new_y
+
+        # deep copy of the modules without the B N^2 factor and the training data
+        saved = (self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle)
+        self.train_inputs = self.train_targets = self._prediction_cache = self._cache_handle = None
+        try:
+            fm = copy.deepcopy(self)
+        finally:
+            self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle = saved
+        fm.train_inputs = (new_x,)
+        fm.train_targets = new_y
+        fm._cache_handle = _PredictionCacheHandle(fm)
+        from ..ops_autograd import register_cache
+        register_cache(fm._cache_handle)
+        if m > _native.lib().gpk_mvn_root_max_n():
+            return fm
+        if N + m <= ops.EXACT_REG_MAX_N:
+            # measured (DESIGN.md §4.6b): up to N' = 256 the fused forward factors the concatenated
+            # data faster than the update's launch chain, so the cache is seeded from scratch
+            fm._train_factor()
+            return fm
+        from .. import library  # noqa: F401  (registers torch.ops.gpk)
+        from ..gp import _exact_append_ladder
+        xn_f = xn.detach().float().contiguous()
+        yn_f = yn.detach().float().contiguous()
+        L2, z2 = _exact_append_ladder(Xb, L, z, hyper, xn_f, yn_f)
+        kern = fm.covar_module
+        key = _version_key(new_x, new_y, kern.raw_outputscale, kern.base_kernel.raw_lengthscale,
+                           fm.mean_module.constant, fm.likelihood.noise_covar.raw_noise)
+        fm._prediction_cache = (key, (_as_batch(new_x).detach().float(), L2, z2, hyper))
+        return fm
 
     def forward(self, x):
         self._check_windows(x)

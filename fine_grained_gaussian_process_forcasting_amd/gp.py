@@ -496,6 +496,37 @@ def _mvn_root_ladder(A: torch.Tensor, max_tries: Optional[int], mean: Optional[t
     raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
 
 
+def _exact_append_ladder(X, L, z, hyper, Xn, yn, max_tries: Optional[int] = None):
+    """psd_safe_cholesky's sequence on gpk::exact_append, as ``_mvn_root_ladder`` runs it on
+    gpk::mvn_root: jitter 0; on any failure the NaN check (NanError), then up to max_tries
+    relaunches of the WHOLE batch with cholesky_jitter * 10^t on the Schur complement's diagonal,
+    each warning NumericalWarning; NotPSDError after the last. Returns (L2, z2). One host read of
+    ``info`` per launch."""
+    def launch(jit):
+        L2, z2, info = torch.ops.gpk.exact_append(X, L, z, hyper, Xn, yn, float(jit))
+        return not bool((info > 0).any()), L2, z2
+
+    ok, L2, z2 = launch(0.0)
+    if ok:
+        return L2, z2
+    for A in (Xn, yn, X, L, z):
+        if torch.isnan(A).any():
+            from .errors import NanError
+            raise NanError(f"cholesky_cpu: {torch.isnan(A).sum().item()} of {A.numel()} elements of the "
+                           f"{tuple(A.shape)} tensor are NaN.")
+    jitter = settings.cholesky_jitter.value(L.dtype)
+    tries = settings.cholesky_max_tries.value() if max_tries is None else max_tries
+    jitter_new = 0.0
+    for i in range(tries):
+        jitter_new = jitter * (10 ** i)
+        warnings.warn(f"A not p.d., added jitter of {jitter_new:.1e} to the diagonal", NumericalWarning)
+        ok, L2, z2 = launch(jitter_new)
+        if ok:
+            return L2, z2
+    from .errors import NotPSDError
+    raise NotPSDError(f"Matrix not positive definite after repeatedly adding jitter up to {jitter_new:.1e}.")
+
+
 def psd_safe_cholesky(A: torch.Tensor, max_tries: Optional[int] = None) -> torch.Tensor:
     """Upstream linear_operator utils/cholesky.py psd_safe_cholesky for a dense matrix (the
     covariance roots of rsample; the hot path's factorisations run in the gfx950 kernels):

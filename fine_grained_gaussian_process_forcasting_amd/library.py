@@ -11,6 +11,7 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::exact_mll_grad(X, L, z, hyper, gout) -> (dX, dy, dhyp)
   gpk::exact_posterior(X, L, z, hyper, Xs) -> (mean, var)                     [eval only]
   gpk::exact_posterior_cov(X, L, z, hyper, Xs) -> (mean, var, cov)            [eval only]
+  gpk::exact_append(X, L, z, hyper, Xn, yn, jitter) -> (L2, z2, info)         [eval only]
   gpk::exact_posterior_train(X, y, hyper, Xs, jitter, max_tries)
       -> (mean, var, cov, L, z, state, info)                                  [autograd]
   gpk::exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov) -> (dX, dy, dXs, dhyp)
@@ -123,6 +124,21 @@ def exact_posterior_cov(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor,
 def _(X, L, z, hyper, Xs):
     B, Ns, _ = Xs.shape
     return Xs.new_empty(B, Ns), Xs.new_empty(B, Ns), Xs.new_empty(B, Ns, Ns)
+
+
+@torch.library.custom_op("gpk::exact_append", mutates_args=(), device_types="cuda")
+def exact_append(X: Tensor, L: Tensor, z: Tensor, hyper: Tensor, Xn: Tensor, yn: Tensor,
+                 jitter: float) -> Tuple[Tensor, Tensor, Tensor]:
+    """-> (L2 (B, N + m, N + m), z2 (B, N + m), info): the cached factor with m observations
+    appended (gpk_exact_append_f32); one rung of the jitter ladder, run by the caller."""
+    return ops.exact_append(X, L, z, hyper, Xn, yn, jitter)
+
+
+@exact_append.register_fake
+def _(X, L, z, hyper, Xn, yn, jitter):
+    B, N, _ = X.shape
+    n2 = N + Xn.shape[1]
+    return X.new_empty(B, n2, n2), X.new_empty(B, n2), X.new_empty(B, dtype=torch.int32)
 
 
 # The differentiable posterior (gpk_exact_mll_f32 for the factor, gpk_exact_posterior_cov_f32 keeping

@@ -305,6 +305,51 @@ def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper
     return (ExactPosteriorCov(mean, var, cov), ws) if return_state else ExactPosteriorCov(mean, var, cov)
 
 
+def exact_append(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch.Tensor, Xn: torch.Tensor,
+                 yn: torch.Tensor, jitter: float = 0.0):
+    """Append the m observations ``Xn`` (B, m, D), ``yn`` (B, m) to the training factor ``L`` and
+    ``z = L^{-1}(y - c)`` of ``exact_mll``: -> (L2 (B, N + m, N + m), z2 (B, N + m), info (B,) int32),
+    the factor and whitened targets of the concatenated data in O(N^2 m), with L2[:, :N, :N] and
+    z2[:, :N] bit-exact copies (one C-ABI call, see include/gpk.h::gpk_exact_append_f32).
+    ``jitter`` is added to the diagonal of the Schur complement beside the noise: one rung of the
+    jitter ladder, which the caller runs (``info[b] > 0``: window b did not factor). ``hyper`` is
+    the exact path's device vector, or (B, 3 + n_ls) with one row per window."""
+    if X.dim() != 3 or Xn.dim() != 3:
+        raise ValueError("X and Xn must be (B, N, D) and (B, m, D)")
+    B, N, D = X.shape
+    if Xn.shape[0] != B or Xn.shape[2] != D:
+        raise ValueError(f"Xn must be (B, m, D) = ({B}, m, {D}), got {tuple(Xn.shape)}")
+    m = Xn.shape[1]
+    if L.shape != (B, N, N) or z.shape != (B, N):
+        raise ValueError("L / z do not match X")
+    if yn.shape != (B, m):
+        raise ValueError(f"yn must be (B, m) = {(B, m)}, got {tuple(yn.shape)}")
+    _require_device(X, L, z, hyper, Xn, yn)
+    X = X.detach().contiguous().float()
+    Xn = Xn.detach().contiguous().float()
+    yn = yn.detach().contiguous().float()
+    L = L.detach().contiguous().float()
+    z = z.detach().contiguous().float()
+    dev = X.device
+    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
+    lib = _native.lib()
+    nbytes = lib.gpk_exact_append_workspace_bytes(B, N, m)
+    if nbytes == 0 and B > 0:
+        raise ValueError(f"gpk_exact_append_f32 does not support B={B}, N={N}, m={m}")
+    ws = torch.empty(max(1, nbytes // 4), device=dev, dtype=torch.float32)
+    L2 = torch.empty(B, N + m, N + m, device=dev, dtype=torch.float32)
+    z2 = torch.empty(B, N + m, device=dev, dtype=torch.float32)
+    info = torch.empty(B, device=dev, dtype=torch.int32)
+    if B == 0:
+        return L2, z2, info
+    rc = lib.gpk_exact_append_perwin_f32(
+        X.data_ptr(), L.data_ptr(), z.data_ptr(), hyper.data_ptr(), n_ls, stride, Xn.data_ptr(), yn.data_ptr(),
+        B, N, m, D, float(jitter), ws.data_ptr(), L2.data_ptr(), z2.data_ptr(), info.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        _native.check(rc, _exact_name("append", stride))
+    return L2, z2, info
+
+
 @dataclass
 class ExactPosteriorGrad:
     dX: Optional[torch.Tensor]    # (B, N, D)

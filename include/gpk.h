@@ -226,6 +226,55 @@ int gpk_exact_posterior_grad_perwin_f32(const float* X, const float* L, const fl
                                         float* dX, float* dy, float* dXs, float* dhyp, void* stream);
 
 /*
+ * Appending observations to a cached exact-GP factor, per window b: from the training factor L
+ * and z = L^{-1}(y - c) of gpk_exact_mll_f32 and m new points (Xn, yn), the factor and whitened
+ * targets of the N' = N + m concatenated points, in O(N^2 m) (nothing is refactored):
+ *   V  = L^{-1} K(X, Xn)                                   (N x m)
+ *   S  = K(Xn, Xn) + (noise + jitter) I - V^T V            (m x m, the Schur complement)
+ *   R  = chol(S)        zn = R^{-1} (yn - c - V^T z)
+ *   L' = [[L, 0], [V^T, R]]        z' = [z ; zn]
+ * By the uniqueness of the Cholesky factor these are what gpk_exact_mll_f32 returns for
+ * ([X ; Xn], [y ; yn]) up to rounding, so every consumer of (L, z) takes them unchanged
+ * (gpk_exact_posterior_f32, gpk_exact_posterior_cov_f32, a further gpk_exact_append_f32).
+ * L'[:N, :N] and z'[:N] are bit-exact copies of the inputs. One launch chain on `stream`: the
+ * joint posterior's two phases at Xn (V, S), the noise of the window's own hyper vector onto
+ * S's diagonal, gpk_mvn_root_f32's factorisation, gpk_tri_solve_f32, and one memory-bound
+ * finish that assembles L' (16-byte stores; V^T through an LDS transpose). One rung of
+ * psd_safe_cholesky's ladder: there is no retry inside, the caller relaunches the whole batch
+ * with jitter * 10^t as for gpk_mvn_root_f32. Fixed order, no atomics: deterministic.
+ *
+ * Replaces (reference): upstream models/exact_gp.py ExactGP.get_fantasy_model ->
+ * exact_prediction_strategies.py get_fantasy_strategy (the low-rank update of the cached
+ * training factor and mean cache), for ExactGPModel (denoising_model/GPModel.py:4-13).
+ *
+ * Memory per call: the workspace, gpk_exact_append_workspace_bytes(B, N, m) bytes (that of
+ * gpk_exact_posterior_cov_f32 at Ns = m, plus B (2 m^2 + 4 m) floats: S, R, the posterior mean
+ * and variance at Xn, the residual and zn), plus the outputs. The query returns 0 for a shape
+ * the call does not accept: 1 <= N, 1 <= m <= gpk_mvn_root_max_n() = 256,
+ * N + m <= gpk_exact_max_n() = 800, B <= 65535 when N > 256 (the blocked phase 1).
+ *
+ * X, L, z, hyp, n_lengthscale : as gpk_exact_posterior_cov_f32 (1 <= D <= 64)
+ * Xn : (B, m, D) float   yn : (B, m) float   jitter : >= 0, added to S's diagonal beside the noise
+ * workspace : device memory of the size above, 16-byte aligned
+ * Lout : (B, N + m, N + m) float out, the full square, upper triangle exactly zero
+ * zout : (B, N + m) float out
+ * info : (B,) int out. 0 = factored; k > 0 = pivot k (1-based) of the Schur complement was not
+ *        positive or was NaN: the new rows of Lout[b] and zout[b] then hold NaN
+ * Returns -(argument index) for an invalid argument (a rejected m or N + m: -10); B == 0 returns 0
+ * and launches nothing. gpk_exact_append_perwin_f32 takes hyp_stride after n_lengthscale as the
+ * other *_perwin_f32 entry points (-6 for a bad stride); stride 0 is gpk_exact_append_f32, bit
+ * for bit.
+ */
+size_t gpk_exact_append_workspace_bytes(int B, int N, int m);
+int gpk_exact_append_f32(const float* X, const float* L, const float* z, const float* hyp, int n_lengthscale,
+                         const float* Xn, const float* yn, int B, int N, int m, int D, float jitter,
+                         void* workspace, float* Lout, float* zout, int* info, void* stream);
+int gpk_exact_append_perwin_f32(const float* X, const float* L, const float* z, const float* hyp,
+                                int n_lengthscale, long long hyp_stride, const float* Xn, const float* yn,
+                                int B, int N, int m, int D, float jitter, void* workspace, float* Lout,
+                                float* zout, int* info, void* stream);
+
+/*
  * Shared inducing-point factorisation of the whitened VariationalStrategy:
  *   A    = K_ZZ + jitter (fp32 add, as K_ZZ.add_jitter), then upcast to fp64
  *   L    = psd_safe_cholesky(A) with the fp64 ladder chol_jitter * 10^t
