@@ -625,14 +625,8 @@ int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const floa
 
 // ---- dense covariance of q(f): phase 1 (A = Linv K_ZX, gpk_variational_cov.hip), then the
 //      variational mode of the covariance kernel (gpk_posterior_cov.hip)
-static bool var_cov_shape_ok(int B, int N, int M) {
-  if (B < 0 || N < 1 || M < 1 || M > 256) return false;
-  const long long T = ((long long)N + 63) / 64;
-  return (long long)B * (T * (T + 1) / 2) <= 0x7fffffffLL;   // one workgroup per tile on grid x
-}
-
 size_t gpk_variational_cov_workspace_bytes(int B, int N, int M) {
-  if (!var_cov_shape_ok(B, N, M)) return 0;
+  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return 0;
   return gpk_var_cov_ws_floats(B, N, M) * sizeof(float);
 }
 
@@ -665,7 +659,7 @@ int gpk_variational_cov_f32(const float* X, const float* Z, const double* Linv, 
   if (D < 1 || D > 64) return -9;
   if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -10;   // A rows are read 16 B at a time
   if (cov == nullptr) return -11;
-  if (!var_cov_shape_ok(B, N, M)) return -7;
+  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return -7;
   if (B == 0) return 0;
   return var_cov_run(X, 0, Z, Linv, vstd, hyp, 1, B, N, M, D, workspace, cov, (hipStream_t)stream);
 }
@@ -685,7 +679,7 @@ int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z
   if (D < 1 || D > 64) return -11;
   if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
   if (cov == nullptr) return -13;
-  if (!var_cov_shape_ok(B, N, M)) return -9;
+  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return -9;
   if (B == 0) return 0;
   return var_cov_run(X, shared_x ? 0LL : (long long)B * N * D, Z, Linv, vstd, hyp, O, B, N, M, D, workspace,
                      cov, (hipStream_t)stream);

@@ -58,6 +58,14 @@ struct GpkVarCovArgs {
 template <bool VAR>
 using GpkCovArgsOf = std::conditional_t<VAR, GpkVarCovArgs, GpkPostCovArgs>;
 size_t gpk_var_cov_ws_floats(int B, int N, int M);
+// Whether the SYRK-shaped phase 2 of a dense covariance of q(f) (mean-field or Cholesky q(u),
+// gpk_var_chol_cov.hip) takes the shape: one workgroup per 64 x 64 tile with tile row <= tile
+// column and window fits grid x.
+inline bool gpk_var_cov_tile_grid_ok(int B, int N, int M) {
+  if (B < 0 || N < 1 || M < 1 || M > 256) return false;
+  const long long T = ((long long)N + 63) / 64;
+  return (long long)B * (T * (T + 1) / 2) <= 0x7fffffffLL;
+}
 int gpk_launch_variational_cov_phase1(const GpkVarCovArgs& a, float* ws, const float* Z, const double* Linv,
                                       int O, hipStream_t stream);
 int gpk_launch_variational_cov_phase2(const GpkVarCovArgs& a, int O, hipStream_t stream);

@@ -43,6 +43,8 @@ constexpr int kCovXS = 64 + 4;        // LDS row stride of the staged test input
 // x / l): the weight vstd_m^2 - 1 is folded into the I-side panel as a chunk is staged, the
 // product is added, and the diagonal is computed here (K_ii = s2 exactly, + jitter). Output o
 // of a batched launch is blockIdx.y.
+// gpk_vcc_syrk_kernel (gpk_var_chol_cov.hip) is this tile with a +-1 row weight over 2 M rows: a
+// shared body takes 2 - 4 SGPRs off all three kernels, so edit them together.
 template <bool VAR>
 __global__ __launch_bounds__(256) void gpk_post_cov_kernel(GpkCovArgsOf<VAR> a) {
   __shared__ float mu[64];

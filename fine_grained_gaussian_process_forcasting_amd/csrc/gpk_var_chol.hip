@@ -27,8 +27,8 @@
 //         panel loop), writes W diag(gvar) for the Gram kernel, forms Y = L_q W row tile by row
 //         tile (panel mt feeds the W tiles kb <= mt) and dA into the shared pipeline's
 //         workspace; row partials of dm, sum gvar, sum gmean and X^T gmean.
-//   gram  one workgroup per (64 x 64 block of the lower triangle, split of the windows), laid
-//         out like gpk_vcg_dlinv_kernel: A (W diag gvar)^T on mfma_f64_16x16x4f64, fp64 partials.
+//   gram  one workgroup per (64 x 64 block of the lower triangle, split of the windows):
+//         vd_lower_gram on A and W diag(gvar), fp64 partials.
 //   finish  every partial summed in fp64 in a fixed order; dX += gmean_i w.
 //   kl    one launch each way, the M^2 sum in a fixed order.
 // O outputs of a multi-output layer run with the output index on grid y of every launch: a
@@ -37,58 +37,19 @@
 // is otherwise the single-output workgroup, so output o has the bits of a single-output call.
 // No atomics in any sum, fixed summation orders: two launches give the same bits; a window's
 // mean / var / dX come from that window's data alone.
+// The blocks this unit runs together with the dense-covariance units -- constants, column means,
+// point staging, the L_q panel staging, the W pass, the Y row tile, the fp64 lower-block Gram --
+// are gpk_var_dense.h's and are described there.
 #include "gpk_common.h"
 #include "gpk_var_chol.h"
+#include "gpk_var_dense.h"
 #include "gpk_variational_cov_grad.h"
 
 #include <mutex>
 
 namespace {
 
-constexpr int kCB = 64;        // points per column block
-constexpr int kKS = 68;        // LDS row stride of a 64-column panel
-constexpr float kNHalfLog2eV = -0.72134752044448170f;  // -0.5 * log2(e)
 constexpr float kMinVar = 1e-6f;
-
-__host__ __device__ constexpr int vch_dq(int D) { return D <= 16 ? 16 : (D <= 32 ? 32 : 64); }
-__host__ __device__ constexpr int vch_max(int a, int b) { return a > b ? a : b; }
-
-// Stage rows 16 kb .. 16 kb + 15 of L_q = tril(C), columns 0 .. 16 kb + 15, into Lp (row
-// stride LS); entries above the diagonal and rows >= M are zeros. Every thread calls it.
-GPK_DEVICE void vch_stage_panel(const float* C, int M, int kb, float* Lp, int LS, int tid) {
-  const int nc = 16 * (kb + 1);
-  for (int e = tid; e < 16 * nc; e += 256) {
-    const int kk = e / nc, m = e - kk * nc;
-    const int k = 16 * kb + kk;
-    const bool ok = k < M && m <= k;
-    const float v = C[ok ? (size_t)k * M + m : 0];
-    Lp[kk * LS + m] = ok ? v : 0.f;
-  }
-}
-
-// W = L_q^T A for this wave's 16 columns: acc[mt][r] = W[16 mt + 4 g + r][16 w + c]. Al holds A
-// (MP x kKS, rows >= M zero). Lane (g, c) feeds, in MFMA step u of panel kb, the A operand
-// L_q[16 kb + 4 g + u][16 mt + c] and the B operand A[16 kb + 4 g + u][16 w + c].
-GPK_DEVICE void vch_w_pass(f32x4 (&acc)[16], const float* Al, float* Lp, const float* C, int M, int MB,
-                           int LS, int tid, int w, int c, int g) {
-#pragma unroll
-  for (int mt = 0; mt < 16; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < MB; ++kb) {
-    lds_barrier();   // the previous panel's reads are done
-    vch_stage_panel(C, M, kb, Lp, LS, tid);
-    lds_barrier();
-    float bv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) bv[u] = Al[(size_t)(16 * kb + 4 * g + u) * kKS + 16 * w + c];
-#pragma unroll
-    for (int mt = 0; mt < 16; ++mt) {
-      if (mt > kb) continue;
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(Lp[(4 * g + u) * LS + 16 * mt + c], bv[u], acc[mt], 0, 0, 0);
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // fwd
@@ -97,11 +58,11 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = a.N, M = a.M, D = a.D;
   const int MP = (M + 15) & ~15, MB = MP >> 4;
-  const int Dq = vch_dq(D);
-  const int lgq = Dq == 16 ? 4 : (Dq == 32 ? 5 : 6);
+  const int Dq = vd_dq(D);
+  const int lgq = vd_lgq(Dq);
   const int ds = Dq + 4;                 // LDS row stride of the staged z / x rows
   const int LS = MP + 4;                 // LDS row stride of an L_q panel
-  const int nst = vch_max(2 * 64 * ds, 16 * LS);
+  const int nst = vd_max(2 * 64 * ds, 16 * LS);
   float* Kl = lds;                       // MP x kKS: K_ZX, then A
   float* zs = Kl + (size_t)MP * kKS;     // 64 x ds   } the L_q panel (16 x LS) lies over
   float* xs = zs + 64 * ds;              // 64 x ds   } these two once K_ZX is formed
@@ -145,45 +106,10 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
   }
   lds_barrier();
 
-  // ---- column means of Z / l, the forward's order
-  for (int e = tid; e < 8 * Dq; e += 256) {
-    const int d = e % Dq, k = e / Dq;
-    float s = 0.f;
-    if (d < D) {
-      const float l = lsc[d];
-#pragma unroll 4
-      for (int m = k; m < M; m += 8) s += Z[(size_t)m * D + d] / l;
-    }
-    scr[e] = s;
-  }
-  lds_barrier();
-  if (tid < 64) {
-    float s = 0.f;
-    if (tid < Dq) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += scr[k * Dq + tid];
-    }
-    cm[tid] = tid < D ? s / (float)M : 0.f;
-  }
-  lds_barrier();
-
-  // ---- this block's points, scaled, centred by the inducing mean, zero padded
-#pragma unroll 4
-  for (int e = tid; e < kCB * Dq; e += 256) {
-    const int j = e >> lgq, d = e & (Dq - 1);
-    const int col = kCB * cb + j;
-    const bool ok = d < D && col < N;
-    const float v = Xb[ok ? (size_t)col * D + d : 0];
-    xs[j * ds + d] = ok ? v / lsc[d] - cm[d] : 0.f;
-  }
-  lds_barrier();
-  if (tid < 64) {
-    float s = 0.f;
-    for (int d = 0; d < Dq; ++d) s = __builtin_fmaf(xs[tid * ds + d], xs[tid * ds + d], s);
-    xn[tid] = s;
-  }
-
-  // ---- K_ZX block, 64 inducing rows at a time
+  vd_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
+  vd_stage_points(Xb, N, D, Dq, cb, lsc, cm, xs, xn, tid);
+  // ---- K_ZX block, 64 inducing rows at a time: in line (the text of gpk_var_cov_a_kernel's), as a
+  //      function it moves this kernel's VGPR count 188 -> 180
   for (int r0 = 0; r0 < MP; r0 += 64) {
     lds_barrier();   // the previous chunk's Gram reads are done (first pass: xn is written)
 #pragma unroll 4
@@ -217,24 +143,24 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
         float dist = zn[p] + xnc - 2.f * acc[r];
         dist = dist < 0.f ? 0.f : dist;
         Kl[(size_t)(r0 + p) * kKS + col] =
-            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2eV * dist) : 0.f;
+            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2e * dist) : 0.f;
       }
     }
   }
   lds_barrier();
 
-  // ---- A = L^{-1} K_ZX for this wave's 16 columns, written over K: row tile rt contracts the
+  // ---- A = L^{-1} K_ZX for this wave's 16 columns (in line in the three forward kernels, see
+  //      gpk_variational_cov.hip's head), written over K: row tile rt contracts the
   //      K tiles kb <= rt, so the tiles go in descending order and a finished tile of A is never
-  //      read as K again. Lane (g, c) feeds the A operand L^{-1}[16 rt + c][16 kb + 4 g + u] and
-  //      the B operand K[16 kb + 4 g + u][16 w + c]; acc[r] = A[16 rt + g + 4 r][16 w + c].
+  //      read as K again
   float* Aw = saved != nullptr ? saved + (size_t)b * M * as : nullptr;
   float* Kc = Kl + 16 * w + c;
   for (int rt = MB - 1; rt >= 0; --rt) {
     const int m = 16 * rt + c;
     const double* row = Linv + (size_t)(m < M ? m : 0) * M;
     // four k blocks' operands (16 loads per lane) are in flight together and the next four are
-    // loaded under these MFMAs, as in phase 1 of gpk_variational_cov.hip: with one workgroup per
-    // CU at M = 256 nothing else hides the L2 latency of a dependent load per block
+    // loaded under these MFMAs: with one workgroup per CU at M = 256 nothing else hides the L2
+    // latency of a dependent load per block
     auto load_a = [&](int kb0, double (&dst)[4][4]) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -258,7 +184,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
       if (kb0 + 4 <= rt) load_a(kb0 + 4, an);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        if (kb0 + q > rt) break;
+        if (kb0 + q > rt) break;   // ascending kb, u: the order of the block-at-a-time loop
 #pragma unroll
         for (int u = 0; u < 4; ++u)
           acc = __builtin_amdgcn_mfma_f64_16x16x4f64(
@@ -276,7 +202,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
 
   // ---- W = L_q^T A (the pass opens with a barrier: A is complete, zs / xs are free)
   f32x4 accW[16];
-  vch_w_pass(accW, Kl, Lp, vchol, M, MB, LS, tid, w, c, g);
+  vd_w_pass(accW, Kl, Lp, vchol, M, MB, LS, tid, w, c, g);
   {
     float s = 0.f;
 #pragma unroll
@@ -323,7 +249,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_fwd_kernel(GpkVarCholArgs a, in
 
 size_t vch_fwd_lds(int M, int D) {
   const int MP = (M + 15) & ~15;
-  const int nst = vch_max(2 * 64 * (vch_dq(D) + 4), 16 * (MP + 4));
+  const int nst = vd_max(2 * 64 * (vd_dq(D) + 4), 16 * (MP + 4));
   return ((size_t)MP * kKS + nst + 6 * 64 + 512 + MP) * sizeof(float);
 }
 
@@ -346,18 +272,17 @@ __host__ VchPlan vch_plan(int B, int N, int M, int D) {
   p.off_dA = off_dA;
   p.MP = (M + 15) & ~15;
   p.ncb = (N + kCB - 1) / kCB;
-  p.WS = B > 32 ? (B + 31) / 32 : 1;
-  p.nsplit = B > 0 ? (B + p.WS - 1) / p.WS : 0;
-  const int nb = (M + 63) / 64;
-  p.npairs = nb * (nb + 1) / 2;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const GpkVarGramSplit sp = gpk_var_gram_split(B, M);
+  p.WS = sp.WS;
+  p.nsplit = sp.nsplit;
+  p.npairs = sp.npairs;
   const size_t nwg = (size_t)B * p.ncb;
-  size_t off = up16(tail);
-  p.off_wg = off; off = up16(off + (size_t)B * M * p.as * sizeof(float));   // W diag(gvar)
-  p.off_dm = off; off = up16(off + nwg * M * sizeof(float));                // sum_i gmean_i A_mi
-  p.off_xg = off; off = up16(off + nwg * 64 * sizeof(float));               // X^T gmean
-  p.off_sc = off; off = up16(off + nwg * 2 * sizeof(float));                // sum gvar, sum gmean
-  p.off_cp = off; off = up16(off + (size_t)p.nsplit * M * M * sizeof(double));
+  size_t off = gpk_up16(tail);
+  p.off_wg = off; off = gpk_up16(off + (size_t)B * M * p.as * sizeof(float));   // W diag(gvar)
+  p.off_dm = off; off = gpk_up16(off + nwg * M * sizeof(float));                // sum_i gmean_i A_mi
+  p.off_xg = off; off = gpk_up16(off + nwg * 64 * sizeof(float));               // X^T gmean
+  p.off_sc = off; off = gpk_up16(off + nwg * 2 * sizeof(float));                // sum gvar, sum gmean
+  p.off_cp = off; off = gpk_up16(off + (size_t)p.nsplit * M * M * sizeof(double));
   p.total = tail == 0 ? 0 : off;
   return p;
 }
@@ -424,7 +349,7 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
 
   // ---- W = L_q^T A (the pass opens with a barrier), kept in LDS; W diag(gvar) -> workspace
   f32x4 accW[16];
-  vch_w_pass(accW, Al, Lp, vchol, M, MB, LS, tid, w, c, g);
+  vd_w_pass(accW, Al, Lp, vchol, M, MB, LS, tid, w, c, g);
   {
     const int col = 16 * w + c;
     const float gvc = gv[col];
@@ -440,19 +365,10 @@ __global__ __launch_bounds__(256) void gpk_vchol_da_kernel(VchAdjArgs k) {
     }
   }
 
-  // ---- Y = L_q W row tile by row tile, dA = gmean m + 2 gvar (Y - A). Lane (g, c) feeds the
-  //      A operand L_q[16 mt + c][16 kb + 4 g + u] and the B operand W[16 kb + 4 g + u][16 w + c].
+  // ---- Y = L_q W row tile by row tile (panel mt feeds the W tiles kb <= mt),
+  //      dA = gmean m + 2 gvar (Y - A)
   for (int mt = 0; mt < MB; ++mt) {
-    lds_barrier();   // the previous panel's reads are done (first pass: W is written)
-    vch_stage_panel(vchol, M, mt, Lp, LS, tid);
-    lds_barrier();
-    f32x4 y = {0.f, 0.f, 0.f, 0.f};
-    for (int kb = 0; kb <= mt; ++kb) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        y = __builtin_amdgcn_mfma_f32_16x16x4f32(Lp[c * LS + 16 * kb + 4 * g + u],
-                                                 Wl[(size_t)(16 * kb + 4 * g + u) * kKS + 16 * w + c], y, 0, 0, 0);
-    }
+    const f32x4 y = vd_lq_row_tile(vchol, M, mt, Lp, LS, Wl, tid, w, c, g);
     const int col = 16 * w + c;
     const float gmc = gm[col], gvc2 = 2.f * gv[col];
 #pragma unroll
@@ -497,61 +413,11 @@ size_t vch_da_lds(int MP) {
 // gram: fp64 partials of sum_b A (W diag gvar)^T, the lower 64 x 64 blocks
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vchol_gram_kernel(VchAdjArgs k) {
-  __shared__ float LA[64 * kKS];
-  __shared__ float LB[64 * kKS];
-  const int N = k.a.N, M = k.a.M, B = k.a.B, as = k.p.as;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = wave_id_uniform();
-  const int c = lane & 15, g = lane >> 4;
-  const int sp = blockIdx.x / k.p.npairs;
-  int pr = blockIdx.x - sp * k.p.npairs;
-  int bi = 0;
-  while (pr > bi) { pr -= bi + 1; ++bi; }
-  const int bj = pr;   // bj <= bi
-  const int b0 = sp * k.p.WS;
-  const int b1 = b0 + k.p.WS < B ? b0 + k.p.WS : B;
+  const int M = k.a.M, as = k.p.as;
   const size_t o = blockIdx.y;
-  const float* Aw = vch_saved(k, o);
-  const float* Wg = vch_ws<float>(k, o, k.p.off_wg);
-  double* Cp = vch_ws<double>(k, o, k.p.off_cp) + (size_t)sp * M * M;
-
-  f64x4 acc[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int b = b0; b < b1; ++b) {
-    const float* Ab = Aw + (size_t)b * M * as;
-    const float* Wb = Wg + (size_t)b * M * as;
-    for (int i0 = 0; i0 < N; i0 += 64) {
-      lds_barrier();
-#pragma unroll 4
-      for (int e = tid; e < 64 * 64; e += 256) {
-        const int r = e >> 6, j = e & 63;
-        const int col = i0 + j, ma = 64 * bi + r, mb = 64 * bj + r;
-        const bool oka = ma < M && col < N, okb = mb < M && col < N;
-        const float va = Ab[oka ? (size_t)ma * as + col : 0];
-        const float vb = Wb[okb ? (size_t)mb * as + col : 0];
-        LA[r * kKS + j] = oka ? va : 0.f;
-        LB[r * kKS + j] = okb ? vb : 0.f;
-      }
-      lds_barrier();
-#pragma unroll 4
-      for (int kk = 0; kk < 16; ++kk) {
-        const double av = (double)LA[(16 * w + c) * kKS + 4 * kk + g];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, (double)LB[(16 * ct + c) * kKS + 4 * kk + g],
-                                                         acc[ct], 0, 0, 0);
-      }
-    }
-  }
-  // acc[ct][r] = block[16 w + g + 4 r][16 ct + c]
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 64 * bi + 16 * w + g + 4 * r, col = 64 * bj + 16 * ct + c;
-      if (row < M && col < M) Cp[(size_t)row * M + col] = acc[ct][r];
-    }
+  const size_t ws = (size_t)M * as;   // floats between two windows' panels
+  vd_lower_gram(vch_saved(k, o), ws, vch_ws<float>(k, o, k.p.off_wg), ws, as, k.a.N, M, k.a.B, k.p.WS,
+                k.p.npairs, vch_ws<double>(k, o, k.p.off_cp));
 }
 
 // ------------------------------------------------------------------------------------------------

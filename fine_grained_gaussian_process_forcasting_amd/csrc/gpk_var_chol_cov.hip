@@ -31,43 +31,29 @@
 //   da    one workgroup per (window, 64-point block): T_W block in LDS, Y = L_q T_W row tile by
 //         row tile (panel mt feeds the tiles kb <= mt), dA = Y - T_A -> the shared workspace.
 //   gram  one workgroup per (64 x 64 block of the lower triangle, split of the windows):
-//         A T_W^T on mfma_f64_16x16x4f64, fp64 partial per split.
+//         vd_lower_gram on the A rows of S and T_W, fp64 partial per split.
 //   finish  dC = tril(sum of the partials) in fp64, fixed order; {ds2, dl} out of the pipeline's row.
 // No atomics in any sum, fixed summation orders: two launches give the same bits; a window's cov
 // and dX come from that window's data alone; output o of a batched launch offsets its base
 // pointers only and has the bits of a single-output call.
+// The blocks this unit runs together with the other dense-covariance and Cholesky units --
+// constants, the L_q panel staging, the Y row tile, the fp64 lower-block Gram -- are
+// gpk_var_dense.h's and are described there; fwd keeps every block in line (see there). syrk stays
+// a copy of gpk_post_cov_kernel (a shared tile body moves the SGPR count of all three kernels, §8.9).
 #include "gpk_common.h"
+#include "gpk_posterior_cov.h"
 #include "gpk_var_chol_cov.h"
+#include "gpk_var_dense.h"
 #include "gpk_variational_cov_grad.h"
 
 #include <mutex>
 
 namespace {
 
-constexpr int kCB = 64;        // points per column block
-constexpr int kKS = 68;        // LDS row stride of a 64-column panel
-constexpr int kHS = 273;       // LDS row stride of a 16-row chunk of H (N <= 256)
 constexpr int kTile = 64;      // output tile edge of syrk
 constexpr int kKC = 32;        // rows of S per LDS chunk of syrk
 constexpr int kVS = kTile + 16;  // LDS row stride of such a chunk (the half's two k rows 16 banks apart)
 constexpr int kXS = 64 + 4;    // LDS row stride of syrk's staged inputs
-constexpr float kNHalfLog2eS = -0.72134752044448170f;  // -0.5 * log2(e)
-
-__host__ __device__ constexpr int vcc_dq(int D) { return D <= 16 ? 16 : (D <= 32 ? 32 : 64); }
-__host__ __device__ constexpr int vcc_max(int a, int b) { return a > b ? a : b; }
-
-// Stage rows 16 kb .. 16 kb + 15 of L_q = tril(C), columns 0 .. 16 kb + 15, into Lp (row
-// stride LS); entries above the diagonal and rows >= M are zeros. Every thread calls it.
-GPK_DEVICE void vcc_stage_panel(const float* C, int M, int kb, float* Lp, int LS, int tid) {
-  const int nc = 16 * (kb + 1);
-  for (int e = tid; e < 16 * nc; e += 256) {
-    const int kk = e / nc, m = e - kk * nc;
-    const int k = 16 * kb + kk;
-    const bool ok = k < M && m <= k;
-    const float v = C[ok ? (size_t)k * M + m : 0];
-    Lp[kk * LS + m] = ok ? v : 0.f;
-  }
-}
 
 struct VccFwdArgs {
   GpkVarCholCovArgs a;
@@ -76,17 +62,21 @@ struct VccFwdArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
-// fwd: S = [W; A] and the window means
+// fwd: S = [W; A] and the window means. Every block in line: the column means and point staging
+// mirror vd_col_means and vd_stage_points, the W pass vd_w_pass (gpk_var_dense.h), the window
+// mean, the K_ZX block and the A row tile those of gpk_var_cov_a_kernel. As calls they move
+// this kernel's register figures, or (means and staging alone) its time at O = 2,
+// B = 256, N = 192, M = 256, D = 32: 1.952 - 1.958 ms against 1.943 - 1.951.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vcc_fwd_kernel(VccFwdArgs k) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = k.a.N, M = k.a.M, D = k.a.D, as = k.as;
   const int MP = (M + 15) & ~15, MB = MP >> 4;
-  const int Dq = vcc_dq(D);
-  const int lgq = Dq == 16 ? 4 : (Dq == 32 ? 5 : 6);
+  const int Dq = vd_dq(D);
+  const int lgq = Dq == 16 ? 4 : (Dq == 32 ? 5 : 6);   // not vd_lgq: the call moves this kernel off the parent's bytes
   const int ds = Dq + 4;                 // LDS row stride of the staged z / x rows
   const int LS = MP + 4;                 // LDS row stride of an L_q panel
-  const int nst = vcc_max(2 * 64 * ds, 16 * LS);
+  const int nst = vd_max(2 * 64 * ds, 16 * LS);
   float* Kl = lds;                       // MP x kKS: K_ZX, then A
   float* zs = Kl + (size_t)MP * kKS;     // 64 x ds   } the L_q panel (16 x LS) lies over
   float* xs = zs + 64 * ds;              // 64 x ds   } these two once K_ZX is formed
@@ -211,7 +201,7 @@ __global__ __launch_bounds__(256) void gpk_vcc_fwd_kernel(VccFwdArgs k) {
         float dist = zn[p] + xnc - 2.f * acc[r];
         dist = dist < 0.f ? 0.f : dist;
         Kl[(size_t)(r0 + p) * kKS + col] =
-            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2eS * dist) : 0.f;
+            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2e * dist) : 0.f;
       }
     }
   }
@@ -275,7 +265,7 @@ __global__ __launch_bounds__(256) void gpk_vcc_fwd_kernel(VccFwdArgs k) {
   for (int mt = 0; mt < 16; ++mt) accW[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int kb = 0; kb < MB; ++kb) {
     lds_barrier();   // the previous panel's reads are done (first pass: A is complete, zs / xs free)
-    vcc_stage_panel(vchol, M, kb, Lp, LS, tid);
+    vd_stage_panel(vchol, M, kb, Lp, LS, tid);
     lds_barrier();
     float bv[4];
 #pragma unroll
@@ -301,7 +291,7 @@ __global__ __launch_bounds__(256) void gpk_vcc_fwd_kernel(VccFwdArgs k) {
 
 size_t vcc_fwd_lds(int M, int D) {
   const int MP = (M + 15) & ~15;
-  const int nst = vcc_max(2 * 64 * (vcc_dq(D) + 4), 16 * (MP + 4));
+  const int nst = vd_max(2 * 64 * (vd_dq(D) + 4), 16 * (MP + 4));
   return ((size_t)MP * kKS + nst + 4 * 64 + 512) * sizeof(float);
 }
 
@@ -408,7 +398,7 @@ __global__ __launch_bounds__(256) void gpk_vcc_syrk_kernel(VccFwdArgs k) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float d2 = __builtin_fmaxf(nI[16 * it + 4 * g + r] + nj - 2.f * G[it][r], 0.f);
-        Kt[it][r] = s2 * __builtin_amdgcn_exp2f(d2 * kNHalfLog2eS);
+        Kt[it][r] = s2 * __builtin_amdgcn_exp2f(d2 * kNHalfLog2e);
       }
   }
 
@@ -474,16 +464,15 @@ __host__ VccPlan vcc_plan(int B, int N, int M, int D) {
   p.off_dA = off_dA;
   p.MP = (M + 15) & ~15;
   p.ncb = (N + kCB - 1) / kCB;
-  p.WS = B > 32 ? (B + 31) / 32 : 1;
-  p.nsplit = B > 0 ? (B + p.WS - 1) / p.WS : 0;
-  const int nb = (M + 63) / 64;
-  p.npairs = nb * (nb + 1) / 2;
+  const GpkVarGramSplit sp = gpk_var_gram_split(B, M);
+  p.WS = sp.WS;
+  p.nsplit = sp.nsplit;
+  p.npairs = sp.npairs;
   p.dps = M + 1 + D;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  size_t off = up16(tail);
-  p.off_T = off;  off = up16(off + (size_t)B * 2 * M * p.as * sizeof(float));    // T = S H
-  p.off_cp = off; off = up16(off + (size_t)p.nsplit * M * M * sizeof(double));   // dC partials
-  p.off_dp = off; off = up16(off + (size_t)p.dps * sizeof(float));               // the pipeline's dpar row
+  size_t off = gpk_up16(tail);
+  p.off_T = off;  off = gpk_up16(off + (size_t)B * 2 * M * p.as * sizeof(float));    // T = S H
+  p.off_cp = off; off = gpk_up16(off + (size_t)p.nsplit * M * M * sizeof(double));   // dC partials
+  p.off_dp = off; off = gpk_up16(off + (size_t)p.dps * sizeof(float));               // the pipeline's dpar row
   p.total = tail == 0 ? 0 : off;
   return p;
 }
@@ -500,7 +489,9 @@ GPK_DEVICE T* vcc_ws(const VccAdjArgs& k, size_t o, size_t off) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// t: T = S H over the stacked rows
+// t: T = S H over the stacked rows. The H-chunk staging and the accumulation are the text of
+// gpk_vcg_t_kernel (gpk_variational_cov_grad.hip) with R = 2 M rows; as one function this kernel
+// spills 21 SGPRs instead of 22, so both stay in line.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vcc_t_kernel(VccAdjArgs k) {
   __shared__ float Hs[16 * kHS];
@@ -594,21 +585,10 @@ __global__ __launch_bounds__(256) void gpk_vcc_da_kernel(VccAdjArgs k) {
     Tl[(size_t)m * kKS + j] = ok ? v : 0.f;
   }
 
-  // ---- Y = L_q T_W row tile by row tile. Lane (g, c) feeds the A operand
-  //      L_q[16 mt + c][16 kb + 4 g + u] and the B operand T_W[16 kb + 4 g + u][16 w + c];
-  //      y[r] = Y[16 mt + 4 g + r][16 w + c]
+  // ---- Y = L_q T_W row tile by row tile (panel mt feeds the tiles kb <= mt), dA = Y - T_A
   const int col = 16 * w + c, gcol = kCB * cb + col;
   for (int mt = 0; mt < MB; ++mt) {
-    lds_barrier();   // the previous panel's reads are done (first pass: T_W is staged)
-    vcc_stage_panel(vchol, M, mt, Lp, LS, tid);
-    lds_barrier();
-    f32x4 y = {0.f, 0.f, 0.f, 0.f};
-    for (int kb = 0; kb <= mt; ++kb) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        y = __builtin_amdgcn_mfma_f32_16x16x4f32(Lp[c * LS + 16 * kb + 4 * g + u],
-                                                 Tl[(size_t)(16 * kb + 4 * g + u) * kKS + col], y, 0, 0, 0);
-    }
+    const f32x4 y = vd_lq_row_tile(vchol, M, mt, Lp, LS, Tl, tid, w, c, g);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int mr = 16 * mt + 4 * g + r;
@@ -627,61 +607,12 @@ size_t vcc_da_lds(int MP) { return ((size_t)MP * kKS + 16 * (MP + 4)) * sizeof(f
 // gram: fp64 partials of sum_b A T_W^T, the lower 64 x 64 blocks
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vcc_gram_kernel(VccAdjArgs k) {
-  __shared__ float LA[64 * kKS];
-  __shared__ float LB[64 * kKS];
-  const int N = k.a.N, M = k.a.M, B = k.a.B, as = k.p.as;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = wave_id_uniform();
-  const int c = lane & 15, g = lane >> 4;
-  const int sp = blockIdx.x / k.p.npairs;
-  int pr = blockIdx.x - sp * k.p.npairs;
-  int bi = 0;
-  while (pr > bi) { pr -= bi + 1; ++bi; }
-  const int bj = pr;   // bj <= bi
-  const int b0 = sp * k.p.WS;
-  const int b1 = b0 + k.p.WS < B ? b0 + k.p.WS : B;
+  const int M = k.a.M, as = k.p.as;
   const size_t o = blockIdx.y;
-  const float* S = k.a.state + o * (size_t)k.state_stride;
-  const float* Tw = vcc_ws<float>(k, o, k.p.off_T);
-  double* Cp = vcc_ws<double>(k, o, k.p.off_cp) + (size_t)sp * M * M;
-
-  f64x4 acc[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int b = b0; b < b1; ++b) {
-    const float* Ab = S + (size_t)b * 2 * M * as + (size_t)M * as;   // the A rows of the window's panel
-    const float* Wb = Tw + (size_t)b * 2 * M * as;                   // T_W
-    for (int i0 = 0; i0 < N; i0 += 64) {
-      lds_barrier();
-#pragma unroll 4
-      for (int e = tid; e < 64 * 64; e += 256) {
-        const int r = e >> 6, j = e & 63;
-        const int col = i0 + j, ma = 64 * bi + r, mb = 64 * bj + r;
-        const bool oka = ma < M && col < N, okb = mb < M && col < N;
-        const float va = Ab[oka ? (size_t)ma * as + col : 0];
-        const float vb = Wb[okb ? (size_t)mb * as + col : 0];
-        LA[r * kKS + j] = oka ? va : 0.f;
-        LB[r * kKS + j] = okb ? vb : 0.f;
-      }
-      lds_barrier();
-#pragma unroll 4
-      for (int kk = 0; kk < 16; ++kk) {
-        const double av = (double)LA[(16 * w + c) * kKS + 4 * kk + g];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, (double)LB[(16 * ct + c) * kKS + 4 * kk + g],
-                                                         acc[ct], 0, 0, 0);
-      }
-    }
-  }
-  // acc[ct][r] = block[16 w + g + 4 r][16 ct + c]
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 64 * bi + 16 * w + g + 4 * r, col = 64 * bj + 16 * ct + c;
-      if (row < M && col < M) Cp[(size_t)row * M + col] = acc[ct][r];
-    }
+  const size_t ws = (size_t)2 * M * as;   // floats between two windows' stacked panels
+  // the A rows of the windows' panels of S against T_W
+  vd_lower_gram(k.a.state + o * (size_t)k.state_stride + (size_t)M * as, ws, vcc_ws<float>(k, o, k.p.off_T), ws,
+                as, k.a.N, M, k.a.B, k.p.WS, k.p.npairs, vcc_ws<double>(k, o, k.p.off_cp));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -708,12 +639,6 @@ __global__ __launch_bounds__(256) void gpk_vcc_finish_kernel(VccAdjArgs k, int n
   if (tid < 1 + D) k.a.dpar[o * (size_t)(1 + D) + tid] = vcc_ws<float>(k, o, k.p.off_dp)[M + tid];
 }
 
-bool vcc_fwd_shape_ok(int B, int N, int M) {
-  if (B < 0 || N < 1 || M < 1 || M > 256) return false;
-  const long long T = ((long long)N + 63) / 64;
-  return (long long)B * (T * (T + 1) / 2) <= 0x7fffffffLL;   // one workgroup per tile on grid x
-}
-
 void vcc_set_lds_once() {
   static std::once_flag once;
   std::call_once(once, [] {
@@ -733,7 +658,7 @@ long long vcc_state_floats(int B, int N, int M) {
 }  // namespace
 
 size_t gpk_var_chol_cov_state_bytes(int B, int N, int M) {
-  if (!vcc_fwd_shape_ok(B, N, M)) return 0;
+  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return 0;
   return (size_t)vcc_state_floats(B, N, M) * sizeof(float);
 }
 
@@ -747,7 +672,7 @@ size_t gpk_var_chol_cov_grad_ws_bytes(int B, int N, int M, int D) {
 }
 
 int gpk_launch_var_chol_cov(const GpkVarCholCovArgs& a, hipStream_t stream) {
-  if (!vcc_fwd_shape_ok(a.B, a.N, a.M) || a.D < 1 || a.D > 64 || a.O < 1 || a.O > 65535) return -7;
+  if (!gpk_var_cov_tile_grid_ok(a.B, a.N, a.M) || a.D < 1 || a.D > 64 || a.O < 1 || a.O > 65535) return -7;
   if (a.B == 0) return 0;
   vcc_set_lds_once();
   const size_t lds = vcc_fwd_lds(a.M, a.D);

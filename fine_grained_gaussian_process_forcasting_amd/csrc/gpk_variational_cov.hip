@@ -13,31 +13,32 @@
 // inputs of a window again.
 //
 // Design: one workgroup of 4 waves per (window, 64-point column block), output o on grid y.
-//   K_ZX block (M x 64): the forward's Gram. z / l centred by the column means of Z / l (the
-//     forward's col_means order: 8 partial sums per column over rows m = k mod 8, then k
-//     ascending), x / l centred by the same means, squared norms by fma over the padded D, the
-//     cross term on fp32 MFMA, d2 = |z|^2 + |x|^2 - 2 z.x clamped at 0, k = s2 exp2(-0.5 log2(e) d2).
-//     The inducing points go through LDS 64 rows at a time (row stride: padded D + 4); the
-//     block stays in LDS with the row stride 68 (the four k rows of an MFMA step land 16 banks apart).
+//   The column means of Z / l, the staging of the block's points and the constants are
+//     gpk_var_dense.h's (vd_col_means, vd_stage_points), which describes them once for the four
+//     units that run them.
+//   K_ZX block (M x 64): the forward's Gram. z / l and x / l centred by the column means of
+//     Z / l, squared norms by fma over the padded D, the cross term on fp32 MFMA, d2 = |z|^2 +
+//     |x|^2 - 2 z.x clamped at 0, k = s2 exp2(-0.5 log2(e) d2). The inducing points go through
+//     LDS 64 rows at a time (row stride: padded D + 4); the block stays in LDS with the row
+//     stride kKS. In line here and in gpk_vchol_fwd_kernel, gpk_vcc_fwd_kernel and
+//     gpk_vcg_q_kernel: as a function it moves the register figures of the other three
+//     (DESIGN.md §8.9); the four copies are the same text.
 //   A = L^{-1} K_ZX: wave w owns the 16 columns w of the block and walks the row tiles; row
 //     tile rt contracts the k blocks kb <= rt only (L^{-1} is lower triangular, its zero blocks
 //     are skipped) with mfma_f64_16x16x4_f64, L^{-1} read from global memory (L2-resident: all
 //     workgroups read the same M x M matrix), four k blocks' operands in flight at a time and
-//     the next four loaded under these MFMAs. The cast to fp32 happens on the store.
+//     the next four loaded under these MFMAs. The cast to fp32 happens on the store. In line here
+//     and in the two Cholesky forward kernels, which walk the row tiles down and write over K:
+//     as a function the row-tile product took 14 SGPRs off this kernel (106 -> 92, §8.9).
 // No atomics, fixed summation order: deterministic. Output o of a batched launch runs the
 // single-output body on its own slices: bit-identical to a single-output call.
 #include "gpk_common.h"
 #include "gpk_posterior_cov.h"
+#include "gpk_var_dense.h"
 
 #include <mutex>
 
 namespace {
-
-constexpr int kCB = 64;        // points per column block
-constexpr int kKS = 68;        // LDS row stride of the K_ZX block
-constexpr float kNHalfLog2eC = -0.72134752044448170f;  // -0.5 * log2(e)
-
-__host__ __device__ constexpr int var_cov_dq(int D) { return D <= 16 ? 16 : (D <= 32 ? 32 : 64); }
 
 struct VarCovP1Args {
   const float* X;
@@ -53,8 +54,8 @@ __global__ __launch_bounds__(256) void gpk_var_cov_a_kernel(VarCovP1Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int N = a.N, M = a.M, D = a.D;
   const int MP = (M + 15) & ~15;
-  const int Dq = var_cov_dq(D);
-  const int lgq = Dq == 16 ? 4 : (Dq == 32 ? 5 : 6);
+  const int Dq = vd_dq(D);
+  const int lgq = vd_lgq(Dq);
   const int ds = Dq + 4;                 // LDS row stride of the staged z / x rows
   float* Kl = lds;                       // MP x kKS
   float* zs = Kl + (size_t)MP * kKS;     // 64 x ds
@@ -83,29 +84,9 @@ __global__ __launch_bounds__(256) void gpk_var_cov_a_kernel(VarCovP1Args a) {
   if (tid < 64) lsc[tid] = tid < D ? hyp[4 + D + tid] : 1.f;
   lds_barrier();
 
-  // ---- column means of Z / l, the forward's order
-  for (int e = tid; e < 8 * Dq; e += 256) {
-    const int d = e % Dq, k = e / Dq;
-    float s = 0.f;
-    if (d < D) {
-      const float l = lsc[d];
-#pragma unroll 4
-      for (int m = k; m < M; m += 8) s += Z[(size_t)m * D + d] / l;
-    }
-    scr[e] = s;
-  }
-  lds_barrier();
-  if (tid < 64) {
-    float s = 0.f;
-    if (tid < Dq) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += scr[k * Dq + tid];
-    }
-    cm[tid] = tid < D ? s / (float)M : 0.f;
-  }
-  lds_barrier();
-
-  // ---- the window's own mean of x / l for phase 2 (one workgroup per window writes it):
+  vd_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
+  // ---- the window's own mean of x / l for phase 2 (one workgroup per window writes it; the
+  //      same text in gpk_vcc_fwd_kernel, gpk_var_chol_cov.hip):
   //      P = 256 / Dq partial sums per column over rows i = k mod P, ascending, then k = 0..P-1
   if (cb == 0) {
     const int d = tid & (Dq - 1), k = tid >> lgq, P = 256 >> lgq;
@@ -125,24 +106,9 @@ __global__ __launch_bounds__(256) void gpk_var_cov_a_kernel(VarCovP1Args a) {
     }
     lds_barrier();
   }
+  vd_stage_points(Xb, N, D, Dq, cb, lsc, cm, xs, xn, tid);
 
-  // ---- this block's points, scaled, centred by the inducing mean, zero padded
-#pragma unroll 4
-  for (int e = tid; e < kCB * Dq; e += 256) {
-    const int j = e >> lgq, d = e & (Dq - 1);
-    const int col = kCB * cb + j;
-    const bool ok = d < D && col < N;
-    const float v = Xb[ok ? (size_t)col * D + d : 0];
-    xs[j * ds + d] = ok ? v / lsc[d] - cm[d] : 0.f;
-  }
-  lds_barrier();
-  if (tid < 64) {
-    float s = 0.f;
-    for (int d = 0; d < Dq; ++d) s = __builtin_fmaf(xs[tid * ds + d], xs[tid * ds + d], s);
-    xn[tid] = s;
-  }
-
-  // ---- K_ZX block, 64 inducing rows at a time
+  // ---- K_ZX block, 64 inducing rows at a time (in line in four kernels, see the file head)
   for (int r0 = 0; r0 < MP; r0 += 64) {
     lds_barrier();   // the previous chunk's Gram reads are done (first pass: xn is written)
 #pragma unroll 4
@@ -176,7 +142,7 @@ __global__ __launch_bounds__(256) void gpk_var_cov_a_kernel(VarCovP1Args a) {
         float dist = zn[p] + xnc - 2.f * acc[r];
         dist = dist < 0.f ? 0.f : dist;
         Kl[(size_t)(r0 + p) * kKS + col] =
-            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2eC * dist) : 0.f;
+            (r0 + p < M && okc) ? s2 * __builtin_amdgcn_exp2f(kNHalfLog2e * dist) : 0.f;
       }
     }
   }
@@ -232,7 +198,7 @@ __global__ __launch_bounds__(256) void gpk_var_cov_a_kernel(VarCovP1Args a) {
 
 size_t var_cov_p1_lds(int M, int D) {
   const int MP = (M + 15) & ~15;
-  return ((size_t)MP * kKS + 2 * 64 * (var_cov_dq(D) + 4) + 4 * 64 + 512) * sizeof(float);
+  return ((size_t)MP * kKS + 2 * 64 * (vd_dq(D) + 4) + 4 * 64 + 512) * sizeof(float);
 }
 
 }  // namespace

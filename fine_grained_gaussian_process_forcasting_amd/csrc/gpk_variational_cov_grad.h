@@ -36,6 +36,24 @@ int gpk_launch_var_cov_grad(const GpkVarCovGradArgs& a, hipStream_t stream);
 // 16, >= the plan's size) after output o - 1's, its dpar row dpar_stride floats (>= M + 1 + D)
 // after; the pipeline writes the head of each.
 size_t gpk_var_cov_grad_tail_plan(int B, int N, int M, int D, size_t* off_dA, int* as);
+
+// What the pipeline's plan and the plans stacked on it (gpk_var_chol.hip, gpk_var_chol_cov.hip)
+// share: the split of an fp64 lower-block Gram over the windows (vd_lower_gram, gpk_var_dense.h)
+// -- WS windows per split (one window each up to B = 32, at most 32 splits), nsplit splits,
+// npairs 64 x 64 blocks in the lower triangle of an M x M matrix -- and the rounding of a byte
+// offset up to 16. Each plan keeps its own offsets.
+struct GpkVarGramSplit {
+  int WS, nsplit, npairs;
+};
+inline GpkVarGramSplit gpk_var_gram_split(int B, int M) {
+  GpkVarGramSplit s;
+  s.WS = B > 32 ? (B + 31) / 32 : 1;
+  s.nsplit = B > 0 ? (B + s.WS - 1) / s.WS : 0;
+  const int nb = (M + 63) / 64;
+  s.npairs = nb * (nb + 1) / 2;
+  return s;
+}
+inline size_t gpk_up16(size_t v) { return (v + 15) & ~(size_t)15; }
 int gpk_launch_var_cov_grad_from_dA(const GpkVarCovGradArgs& a, size_t ws_stride, int dpar_stride,
                                     hipStream_t stream);
 

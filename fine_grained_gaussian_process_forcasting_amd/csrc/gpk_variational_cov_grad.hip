@@ -25,7 +25,7 @@
 //        Q x, Q^T z and the row / column sums of Q (a ones operand) on the MFMA; writes this
 //        part of dX and per-workgroup partials of U, sum Q and sum xt V.
 //   dlinv one workgroup per (64 x 64 block of the lower triangle, split of the windows):
-//        dA K_ZX^T on mfma_f64_16x16x4f64 from LDS panels, fp64 partial per split.
+//        vd_lower_gram on dA and K_ZX, fp64 partial per split.
 //   kxx  one workgroup per (chunk of windows, 64-row tile row of cov): K_XX tile by tile as the
 //        forward's phase 2 computes it, P in LDS, P x and the row sums on the MFMA; subtracts its
 //        part from dX (this launch follows q on the stream) and writes partials of dl and ds2.
@@ -33,20 +33,18 @@
 // No atomics, no host synchronisation, fixed summation orders: two launches give the same bits;
 // a window's dX comes from that window's data alone; the chunking depends on (B, N, M, D) only,
 // so output o of a batched launch has the bits of a single-output call.
+// The blocks this unit runs together with the forward and the Cholesky units -- constants,
+// column means, point staging, the fp64 lower-block Gram of dlinv -- are gpk_var_dense.h's and are
+// described there.
 #include "gpk_common.h"
 #include "gpk_variational_cov_grad.h"
+#include "gpk_var_dense.h"
 
 #include <mutex>
 
 namespace {
 
-constexpr int kCB = 64;        // points per column block
-constexpr int kKS = 68;        // LDS row stride of a 64-column panel
-constexpr int kHS = 273;       // LDS row stride of a 16-row chunk of H (N <= 256)
 constexpr int kMaxN = 256;
-constexpr float kNHalfLog2e = -0.72134752044448170f;  // -0.5 * log2(e)
-
-__host__ __device__ constexpr int vcg_dq(int D) { return D <= 16 ? 16 : (D <= 32 ? 32 : 64); }
 
 // Workspace slice of one output (byte offsets, each a multiple of 16) and the work split.
 struct VcgPlan {
@@ -61,27 +59,26 @@ __host__ VcgPlan vcg_plan(int B, int N, int M, int D) {
   VcgPlan p;
   p.as = (N + 63) / 64 * 64;
   p.MP = (M + 15) & ~15;
-  p.Dq = vcg_dq(D);
+  p.Dq = vd_dq(D);
   p.ncb = (N + kCB - 1) / kCB;
   p.WC = B > 64 ? (B + 63) / 64 : 1;
   p.nchunk = B > 0 ? (B + p.WC - 1) / p.WC : 0;
-  p.WS = B > 32 ? (B + 31) / 32 : 1;
-  p.nsplit = B > 0 ? (B + p.WS - 1) / p.WS : 0;
-  const int nb = (M + 63) / 64;
-  p.npairs = nb * (nb + 1) / 2;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const GpkVarGramSplit sp = gpk_var_gram_split(B, M);
+  p.WS = sp.WS;
+  p.nsplit = sp.nsplit;
+  p.npairs = sp.npairs;
   size_t off = 0;
-  p.off_dp = off; off = up16(off + (size_t)p.nsplit * M * M * sizeof(double));
-  p.off_uz = off; off = up16(off + (size_t)M * 64 * sizeof(double));
-  p.off_qt = off; off = up16(off + (size_t)M * sizeof(double));
-  p.off_dA = off; off = up16(off + (size_t)B * M * p.as * sizeof(float));
-  p.off_K = off;  off = up16(off + (size_t)B * M * p.as * sizeof(float));
-  p.off_dw = off; off = up16(off + (size_t)B * M * sizeof(float));
+  p.off_dp = off; off = gpk_up16(off + (size_t)p.nsplit * M * M * sizeof(double));
+  p.off_uz = off; off = gpk_up16(off + (size_t)M * 64 * sizeof(double));
+  p.off_qt = off; off = gpk_up16(off + (size_t)M * sizeof(double));
+  p.off_dA = off; off = gpk_up16(off + (size_t)B * M * p.as * sizeof(float));
+  p.off_K = off;  off = gpk_up16(off + (size_t)B * M * p.as * sizeof(float));
+  p.off_dw = off; off = gpk_up16(off + (size_t)B * M * sizeof(float));
   const size_t nwg = (size_t)p.nchunk * p.ncb;
-  p.off_up = off; off = up16(off + nwg * p.MP * p.Dq * sizeof(float));
-  p.off_qr = off; off = up16(off + nwg * p.MP * sizeof(float));
-  p.off_xv = off; off = up16(off + nwg * 64 * sizeof(float));
-  p.off_cp = off; off = up16(off + nwg * 128 * sizeof(float));
+  p.off_up = off; off = gpk_up16(off + nwg * p.MP * p.Dq * sizeof(float));
+  p.off_qr = off; off = gpk_up16(off + nwg * p.MP * sizeof(float));
+  p.off_xv = off; off = gpk_up16(off + nwg * 64 * sizeof(float));
+  p.off_cp = off; off = gpk_up16(off + nwg * 128 * sizeof(float));
   p.total = off;
   return p;
 }
@@ -99,38 +96,14 @@ GPK_DEVICE T* vcg_ws(const VcgArgs& k, size_t o, size_t off) {
   return (T*)((char*)k.a.ws + o * k.ws_stride + off);
 }
 
-// Column means of Z / l in the forward's order: 8 partial sums per column over rows m = k mod 8,
-// then k ascending. Every thread of the workgroup calls it; scr holds 8 * Dq floats.
-GPK_DEVICE void vcg_col_means(const float* Z, int M, int D, int Dq, const float* lsc, float* scr, float* cm,
-                              int tid) {
-  for (int e = tid; e < 8 * Dq; e += 256) {
-    const int d = e % Dq, k = e / Dq;
-    float s = 0.f;
-    if (d < D) {
-      const float l = lsc[d];
-#pragma unroll 4
-      for (int m = k; m < M; m += 8) s += Z[(size_t)m * D + d] / l;
-    }
-    scr[e] = s;
-  }
-  lds_barrier();
-  if (tid < 64) {
-    float s = 0.f;
-    if (tid < Dq) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) s += scr[k * Dq + tid];
-    }
-    cm[tid] = tid < D ? s / (float)M : 0.f;
-  }
-  lds_barrier();
-}
-
 // Row tile of the mi-th tile a wave owns: 0 1 2 3 3 2 1 0 0 1 2 3 3 2 1 0 over the waves (the
 // triangular dK product of tile row mt costs MB - mt tile products).
 GPK_DEVICE int vcg_row_tile(int mi, int w) { return 8 * (mi >> 1) + ((mi & 1) ? 7 - w : w); }
 
 // ------------------------------------------------------------------------------------------------
-// t: T = A H, dw, dA
+// t: T = A H, dw, dA. The H-chunk staging and the accumulation are the text of gpk_vcc_t_kernel
+// (gpk_var_chol_cov.hip, R = 2 M rows): as one function that kernel spills 21 SGPRs instead of
+// 22, so both stay in line; edit them together.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vcg_t_kernel(VcgArgs k) {
   __shared__ float Hs[16 * kHS];
@@ -250,7 +223,7 @@ __global__ __launch_bounds__(256) void gpk_vcg_q_kernel(VcgArgs k) {
 
   if (tid < 64) lsc[tid] = tid < D ? hyp[4 + D + tid] : 1.f;
   lds_barrier();
-  vcg_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
+  vd_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
 
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 accU[4][DT], accQr[4];
@@ -271,23 +244,10 @@ __global__ __launch_bounds__(256) void gpk_vcg_q_kernel(VcgArgs k) {
     float* dXb = k.a.dX + (o * (size_t)B + b) * (size_t)N * D;
 
     lds_barrier();   // the previous window's reads of xs and Kl are done
-    // ---- this block's points, scaled, centred by the inducing mean, zero padded
-#pragma unroll 4
-    for (int e = tid; e < kCB * Dq; e += 256) {
-      const int j = e >> lgq, d = e & (Dq - 1);
-      const int col = kCB * cb + j;
-      const bool ok = d < D && col < N;
-      const float v = Xb[ok ? (size_t)col * D + d : 0];
-      xs[j * ds + d] = ok ? v / lsc[d] - cm[d] : 0.f;
-    }
-    lds_barrier();
-    if (tid < 64) {
-      float s = 0.f;
-      for (int d = 0; d < Dq; ++d) s = __builtin_fmaf(xs[tid * ds + d], xs[tid * ds + d], s);
-      xn[tid] = s;
-    }
-
-    // ---- K_ZX block, 64 inducing rows at a time (the forward's arithmetic)
+    vd_stage_points(Xb, N, D, Dq, cb, lsc, cm, xs, xn, tid);
+    // ---- K_ZX block, 64 inducing rows at a time (the forward's arithmetic): in line (the text of
+    //      gpk_var_cov_a_kernel's with Dq at compile time), as a function it moves q<2>'s VGPR count
+    //      264 -> 268 and SGPR spills
     for (int r0 = 0; r0 < MP; r0 += 64) {
       lds_barrier();
 #pragma unroll 4
@@ -468,61 +428,11 @@ size_t vcg_q_lds(int MP, int Dq) {
 // dlinv: fp64 partials of sum_b dA K_ZX^T
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gpk_vcg_dlinv_kernel(VcgArgs k) {
-  __shared__ float LA[64 * kKS];
-  __shared__ float LB[64 * kKS];
-  const int N = k.a.N, M = k.a.M, B = k.a.B, as = k.p.as;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = wave_id_uniform();
-  const int c = lane & 15, g = lane >> 4;
-  const int sp = blockIdx.x / k.p.npairs;
-  int pr = blockIdx.x - sp * k.p.npairs;
-  int bi = 0;
-  while (pr > bi) { pr -= bi + 1; ++bi; }
-  const int bj = pr;   // bj <= bi
+  const int M = k.a.M, as = k.p.as;
   const size_t o = blockIdx.y;
-  const int b0 = sp * k.p.WS;
-  const int b1 = b0 + k.p.WS < B ? b0 + k.p.WS : B;
-  const float* dA = vcg_ws<float>(k, o, k.p.off_dA);
-  const float* Kw = vcg_ws<float>(k, o, k.p.off_K);
-  double* Dp = vcg_ws<double>(k, o, k.p.off_dp) + (size_t)sp * M * M;
-
-  f64x4 acc[4];
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct) acc[ct] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int b = b0; b < b1; ++b) {
-    const float* dAb = dA + (size_t)b * M * as;
-    const float* Kb = Kw + (size_t)b * M * as;
-    for (int i0 = 0; i0 < N; i0 += 64) {
-      lds_barrier();
-#pragma unroll 4
-      for (int e = tid; e < 64 * 64; e += 256) {
-        const int r = e >> 6, j = e & 63;
-        const int col = i0 + j, ma = 64 * bi + r, mb = 64 * bj + r;
-        const bool oka = ma < M && col < N, okb = mb < M && col < N;
-        const float va = dAb[oka ? (size_t)ma * as + col : 0];
-        const float vb = Kb[okb ? (size_t)mb * as + col : 0];
-        LA[r * kKS + j] = oka ? va : 0.f;
-        LB[r * kKS + j] = okb ? vb : 0.f;
-      }
-      lds_barrier();
-#pragma unroll 4
-      for (int kk = 0; kk < 16; ++kk) {
-        const double av = (double)LA[(16 * w + c) * kKS + 4 * kk + g];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, (double)LB[(16 * ct + c) * kKS + 4 * kk + g],
-                                                         acc[ct], 0, 0, 0);
-      }
-    }
-  }
-  // acc[ct][r] = block[16 w + g + 4 r][16 ct + c]
-#pragma unroll
-  for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 64 * bi + 16 * w + g + 4 * r, col = 64 * bj + 16 * ct + c;
-      if (row < M && col < M) Dp[(size_t)row * M + col] = acc[ct][r];
-    }
+  const size_t ws = (size_t)M * as;   // floats between two windows' panels
+  vd_lower_gram(vcg_ws<float>(k, o, k.p.off_dA), ws, vcg_ws<float>(k, o, k.p.off_K), ws, as, k.a.N, M, k.a.B,
+                k.p.WS, k.p.npairs, vcg_ws<double>(k, o, k.p.off_dp));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -688,7 +598,7 @@ __global__ __launch_bounds__(256) void gpk_vcg_reduce_kernel(VcgArgs k) {
   const float* Z = k.a.Z + o * (size_t)M * D;
   if (tid < 64) lsc[tid] = tid < D ? hyp[4 + D + tid] : 1.f;
   lds_barrier();
-  vcg_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
+  vd_col_means(Z, M, D, Dq, lsc, scr, cm, tid);
 
   const long long e = (long long)blockIdx.x * 256 + tid;
   const long long mm = (long long)M * M;

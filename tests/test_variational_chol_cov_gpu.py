@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 JIT = 1e-4
 SHAPES = [(2, 1, 8, 3), (2, 16, 20, 6), (3, 17, 16, 4), (2, 65, 64, 5), (2, 64, 130, 8), (2, 192, 256, 32),
-          (1, 256, 64, 64)]
+          (1, 256, 64, 64), (2, 70, 37, 17), (2, 70, 37, 33)]
 BLOCKS = ("dX", "dLinv", "dZ", "dchol", "ds2", "dls")
 
 

@@ -14,7 +14,8 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-4
 JIT = 1e-4
 
-SHAPES = [(3, 20, 8, 4), (2, 65, 20, 5), (2, 64, 64, 32), (1, 96, 80, 16), (2, 192, 256, 32), (1, 256, 256, 64)]
+SHAPES = [(3, 20, 8, 4), (2, 65, 20, 5), (2, 64, 64, 32), (1, 96, 80, 16), (2, 192, 256, 32), (1, 256, 256, 64),
+          (2, 70, 37, 17), (2, 70, 37, 33)]
 
 
 def _rel(a, b):

@@ -74,7 +74,8 @@ def _check(got, want, skip=()):
 
 
 @pytest.mark.parametrize("B,N,M,D", [(2, 1, 8, 3), (2, 16, 20, 6), (3, 17, 16, 4), (2, 65, 64, 5),
-                                     (2, 64, 130, 8), (2, 192, 256, 32), (1, 256, 64, 64)])
+                                     (2, 64, 130, 8), (2, 192, 256, 32), (1, 256, 64, 64),
+                                     (2, 70, 37, 17), (2, 70, 37, 33)])
 def test_cov_grad_parity(cuda_device, B, N, M, D):
     from fine_grained_gaussian_process_forcasting_amd import ops
     dev = cuda_device
