@@ -68,6 +68,8 @@ SIGNATURES = {
     "gpk_exact_append_perwin_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong,
                                             c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_float,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpk_exact_drop_max_m": (c_int, []),
+    "gpk_exact_drop_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_chol_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_float, c_double, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpk_kzz_backward_workspace_bytes": (c_size_t, [c_int, c_int]),

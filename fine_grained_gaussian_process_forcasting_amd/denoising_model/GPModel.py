@@ -22,7 +22,11 @@ returns the posterior there.
 
 ``model.get_fantasy_model(new_x, new_y)`` conditions a model that has predicted on later
 observations without fitting again: gpk_exact_append_f32 extends the cached factor by the new
-points and the returned model starts with that cache.
+points and the returned model starts with that cache. ``model.forget_oldest(m)`` is the other half
+of a streaming look-back: gpk_exact_drop_f32 takes the m oldest points out of the cached factor
+(a rank-m update of the trailing block), and ``model.get_sliding_model(new_x, new_y)`` does both,
+so a window of constant N slides over a stream with no factorisation launch, also at N = 800
+where ``get_fantasy_model`` alone has no room.
 
 Inputs may be batched (B, N, D) windows, a single (N, D) window or 1-D (N,) points,
 as GPyTorch accepts; targets follow (B, N) / (N,).
@@ -50,6 +54,11 @@ from ..errors import GPInputWarning
 from ..gp import ConstantMean, MultivariateNormal, RBFKernel, ScaleKernel, _per_window, psd_safe_cholesky
 
 
+# forget_oldest uses the rank-m update when more than this many points are kept; up to it one fused
+# forward on the kept data seeds the cache faster (measured: DESIGN.md §4.6c)
+EXACT_DROP_MIN_KEPT = ops.EXACT_REG_MAX_N
+
+
 def _as_batch(x: torch.Tensor) -> torch.Tensor:
     """(N,) -> (1, N, 1); (N, D) -> (1, N, D); (B, N, D) unchanged."""
     if x.dim() == 1:
@@ -72,6 +81,10 @@ class _PredictionCacheHandle:
         m = self._model()
         if m is not None:
             m._prediction_cache = None
+
+
+_NO_CACHE_MSG = ("Fantasy observations can only be added after making predictions with a model so "
+                 "that all test independent caches exist. Call the model on some data first!")
 
 
 def _version_key(*ts):
@@ -153,33 +166,10 @@ class ExactGPModel(nn.Module):
         (gpk_mvn_root_max_n) give the new model without a seeded cache: its first eval call
         factors from scratch. The Schur complement's factorisation runs psd_safe_cholesky's jitter
         ladder (NumericalWarning per retry, NanError, NotPSDError)."""
-        if kwargs.get("noise") is not None:
-            raise NotImplementedError("get_fantasy_model(noise=...) belongs to FixedNoiseGaussianLikelihood, "
-                                      "which this package does not have")
-        x = inputs[0] if isinstance(inputs, (tuple, list)) else inputs
-        xn = _as_batch(x)
-        lead = 0 if x.dim() < 3 else 1                 # batch dimensions of the inputs
-        if targets.dim() == lead + 2:
-            raise NotImplementedError("a batch of fantasies (targets with one more leading dimension than the "
-                                      "inputs) is not supported: add one set of observations per window")
-        if targets.dim() != lead + 1 and not (lead == 1 and targets.dim() == 1):
-            raise ValueError(f"targets must be (m,) or (B, m), got {tuple(targets.shape)}")
-        if self._prediction_cache is None:
-            raise RuntimeError("Fantasy observations can only be added after making predictions with a model so "
-                               "that all test independent caches exist. Call the model on some data first!")
-        self._check_windows(x)
+        x, xn, yn, m = self._fantasy_args(inputs, targets, kwargs)
         train_x, train_y = self.train_inputs[0], self.train_targets
         Xb, L, z, hyper = self._train_factor()         # the cache, or a refit if it went stale
         B, N, D = Xb.shape
-        if xn.shape[-1] != D or xn.shape[0] not in (1, B):
-            raise ValueError(f"inputs of shape {tuple(x.shape)} do not match the training inputs "
-                             f"{tuple(train_x.shape)}")
-        m = xn.shape[1]
-        xn = xn.expand(B, m, D)
-        if targets.shape[-1] != m or (targets.dim() == 2 and targets.shape[0] != B):
-            raise ValueError(f"targets of shape {tuple(targets.shape)} do not match {m} new point(s) in {B} "
-                             "window(s)")
-        yn = targets.expand(B, m) if targets.dim() == 1 else targets
         from .. import _native
         if N + m > _native.lib().gpk_exact_max_n():
             _native.check(-6, ops._exact_name("mll", hyper.dim() - 1))    # what ops.exact_mll raises for N + m
@@ -189,18 +179,7 @@ class ExactGPModel(nn.Module):
         new_y = torch.cat([train_y.reshape(B, N), yn.to(train_y.dtype)], dim=1)
         new_y = new_y.reshape(-1) if train_y.dim() == 1 else new_y
 
-        # deep copy of the modules without the B N^2 factor and the training data
-        saved = (self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle)
-        self.train_inputs = self.train_targets = self._prediction_cache = self._cache_handle = None
-        try:
-            fm = copy.deepcopy(self)
-        finally:
-            self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle = saved
-        fm.train_inputs = (new_x,)
-        fm.train_targets = new_y
-        fm._cache_handle = _PredictionCacheHandle(fm)
-        from ..ops_autograd import register_cache
-        register_cache(fm._cache_handle)
+        fm = self._clone_with_data(new_x, new_y)
         if m > _native.lib().gpk_mvn_root_max_n():
             return fm
         if N + m <= ops.EXACT_REG_MAX_N:
@@ -213,11 +192,112 @@ class ExactGPModel(nn.Module):
         xn_f = xn.detach().float().contiguous()
         yn_f = yn.detach().float().contiguous()
         L2, z2 = _exact_append_ladder(Xb, L, z, hyper, xn_f, yn_f)
-        kern = fm.covar_module
-        key = _version_key(new_x, new_y, kern.raw_outputscale, kern.base_kernel.raw_lengthscale,
-                           fm.mean_module.constant, fm.likelihood.noise_covar.raw_noise)
-        fm._prediction_cache = (key, (_as_batch(new_x).detach().float(), L2, z2, hyper))
+        fm._seed_cache(L2, z2, hyper)
         return fm
+
+    def _fantasy_args(self, inputs, targets, kwargs):
+        """get_fantasy_model's argument checks, before any launch: -> (x, xn (B, m, D), yn (B, m), m)."""
+        if kwargs.get("noise") is not None:
+            raise NotImplementedError("get_fantasy_model(noise=...) belongs to FixedNoiseGaussianLikelihood, "
+                                      "which this package does not have")
+        x = inputs[0] if isinstance(inputs, (tuple, list)) else inputs
+        xn = _as_batch(x)
+        lead = 0 if x.dim() < 3 else 1                 # batch dimensions of the inputs
+        if targets.dim() == lead + 2:
+            raise NotImplementedError("a batch of fantasies (targets with one more leading dimension than the "
+                                      "inputs) is not supported: add one set of observations per window")
+        if targets.dim() != lead + 1 and not (lead == 1 and targets.dim() == 1):
+            raise ValueError(f"targets must be (m,) or (B, m), got {tuple(targets.shape)}")
+        if self._prediction_cache is None:
+            raise RuntimeError(_NO_CACHE_MSG)
+        self._check_windows(x)
+        train_x = self.train_inputs[0]
+        B, N, D = _as_batch(train_x).shape
+        if xn.shape[-1] != D or xn.shape[0] not in (1, B):
+            raise ValueError(f"inputs of shape {tuple(x.shape)} do not match the training inputs "
+                             f"{tuple(train_x.shape)}")
+        m = xn.shape[1]
+        xn = xn.expand(B, m, D)
+        if targets.shape[-1] != m or (targets.dim() == 2 and targets.shape[0] != B):
+            raise ValueError(f"targets of shape {tuple(targets.shape)} do not match {m} new point(s) in {B} "
+                             "window(s)")
+        yn = targets.expand(B, m) if targets.dim() == 1 else targets
+        return x, xn, yn, m
+
+    def _clone_with_data(self, new_x, new_y):
+        """A deep copy of the modules (parameters included) with (new_x, new_y) as training data, a
+        prediction-cache handle of its own and no cache; the B N^2 factor and the training data are
+        taken off before the copy."""
+        saved = (self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle)
+        self.train_inputs = self.train_targets = self._prediction_cache = self._cache_handle = None
+        try:
+            fm = copy.deepcopy(self)
+        finally:
+            self.train_inputs, self.train_targets, self._prediction_cache, self._cache_handle = saved
+        fm.train_inputs = (new_x,)
+        fm.train_targets = new_y
+        fm._cache_handle = _PredictionCacheHandle(fm)
+        from ..ops_autograd import register_cache
+        register_cache(fm._cache_handle)
+        return fm
+
+    def _seed_cache(self, L, z, hyper):
+        """Start with (L, z) as the prediction cache of the current training data and parameters."""
+        train_x, train_y = self.train_inputs[0], self.train_targets
+        kern = self.covar_module
+        key = _version_key(train_x, train_y, kern.raw_outputscale, kern.base_kernel.raw_lengthscale,
+                           self.mean_module.constant, self.likelihood.noise_covar.raw_noise)
+        self._prediction_cache = (key, (_as_batch(train_x).detach().float(), L, z, hyper))
+
+    def forget_oldest(self, m):
+        """A new model whose training data are the last N - m points of every window (the oldest
+        are the first along the point axis, the end ``get_fantasy_model`` does not append to),
+        without fitting again: one gpk::exact_drop call (include/gpk.h::gpk_exact_drop_f32) turns
+        the cached factor L and z = L^{-1}(y - c) into those of the kept points, a rank-m update of
+        the trailing block in O((N - m)^2 m) that cannot fail, and seeds the new model's prediction
+        cache. Upstream GPyTorch has no counterpart; with ``get_fantasy_model`` it makes a look-back
+        of constant length (``get_sliding_model``).
+
+        ``get_fantasy_model``'s contract: the model must have been called in eval mode since the
+        last ``train()`` / ``set_train_data`` (RuntimeError otherwise); the result is a deep copy of
+        the modules with contiguous copies of the kept ``train_inputs`` / ``train_targets`` and a
+        cache handle of its own; this model and its cache are left untouched. 1 <= m < N, otherwise
+        ValueError. The update is used for m <= 64 (gpk_exact_drop_max_m) where it was measured
+        faster than factoring the kept points (N - m > 256); otherwise the cache
+        is seeded by one factorisation of the kept data. With gradients the new model behaves as
+        any model with that training data (the eval path under grad refits from the live
+        parameters)."""
+        if self._prediction_cache is None:
+            raise RuntimeError(_NO_CACHE_MSG)
+        m = int(m)
+        train_x, train_y = self.train_inputs[0], self.train_targets
+        N = _as_batch(train_x).shape[1]
+        if m < 1 or m >= N:
+            raise ValueError(f"m must be in 1 .. N - 1 = {N - 1}, got {m}")
+        Xb, L, z, hyper = self._train_factor()         # the cache, or a refit if it went stale
+        new_x = (train_x[:, m:] if train_x.dim() == 3 else train_x[m:]).clone()
+        new_y = train_y[..., m:].clone()
+        fm = self._clone_with_data(new_x, new_y)
+        from .. import _native
+        if m > _native.lib().gpk_exact_drop_max_m() or N - m <= EXACT_DROP_MIN_KEPT:
+            fm._train_factor()
+            return fm
+        from .. import library  # noqa: F401  (registers torch.ops.gpk)
+        L2, z2 = torch.ops.gpk.exact_drop(L, z, m)
+        fm._seed_cache(L2, z2, hyper)
+        return fm
+
+    def get_sliding_model(self, inputs, targets, **kwargs):
+        """``forget_oldest(m).get_fantasy_model(inputs, targets)`` with m the number of new points:
+        the look-back keeps its length N while it takes the m newest observations and forgets the m
+        oldest, with no factorisation launch where both updates apply. Works at N = 800
+        (gpk_exact_max_n), where ``get_fantasy_model`` alone raises. Arguments and errors as
+        ``get_fantasy_model``, checked before any launch; m < N."""
+        _, _, _, m = self._fantasy_args(inputs, targets, kwargs)
+        N = _as_batch(self.train_inputs[0]).shape[1]
+        if m >= N:
+            raise ValueError(f"{m} new point(s) would replace all {N} training point(s) of a window")
+        return self.forget_oldest(m).get_fantasy_model(inputs, targets, **kwargs)
 
     def forward(self, x):
         self._check_windows(x)

@@ -12,6 +12,7 @@ instead of being opaque Python. Each op is one C-ABI call of include/gpk.h on
   gpk::exact_posterior(X, L, z, hyper, Xs) -> (mean, var)                     [eval only]
   gpk::exact_posterior_cov(X, L, z, hyper, Xs) -> (mean, var, cov)            [eval only]
   gpk::exact_append(X, L, z, hyper, Xn, yn, jitter) -> (L2, z2, info)         [eval only]
+  gpk::exact_drop(L, z, m) -> (L2, z2)                                        [eval only]
   gpk::exact_posterior_train(X, y, hyper, Xs, jitter, max_tries)
       -> (mean, var, cov, L, z, state, info)                                  [autograd]
   gpk::exact_posterior_grad(X, L, z, hyper, Xs, state, gmean, gvar, gcov) -> (dX, dy, dXs, dhyp)
@@ -139,6 +140,19 @@ def _(X, L, z, hyper, Xn, yn, jitter):
     B, N, _ = X.shape
     n2 = N + Xn.shape[1]
     return X.new_empty(B, n2, n2), X.new_empty(B, n2), X.new_empty(B, dtype=torch.int32)
+
+
+@torch.library.custom_op("gpk::exact_drop", mutates_args=(), device_types="cuda")
+def exact_drop(L: Tensor, z: Tensor, m: int) -> Tuple[Tensor, Tensor]:
+    """-> (L2 (B, N - m, N - m), z2 (B, N - m)): the cached factor without its m oldest observations
+    (gpk_exact_drop_f32), a rank-m update of the trailing block; no hyper-parameters enter."""
+    return ops.exact_drop(L, z, m)
+
+
+@exact_drop.register_fake
+def _(L, z, m):
+    B, N, _ = L.shape
+    return L.new_empty(B, N - m, N - m), L.new_empty(B, N - m)
 
 
 # The differentiable posterior (gpk_exact_mll_f32 for the factor, gpk_exact_posterior_cov_f32 keeping

@@ -350,6 +350,37 @@ def exact_append(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch
     return L2, z2, info
 
 
+def exact_drop(L: torch.Tensor, z: torch.Tensor, m: int):
+    """Drop the m oldest (first) observations from the training factor ``L`` (B, N, N) and
+    ``z = L^{-1}(y - c)`` (B, N) of ``exact_mll`` / ``exact_append``: -> (L2 (B, N - m, N - m),
+    z2 (B, N - m)), the factor and whitened targets of the last N - m points in O((N - m)^2 m), a
+    positive rank-m update of the trailing block that cannot fail (one C-ABI call, see
+    include/gpk.h::gpk_exact_drop_f32). Neither the inputs nor the hyper-parameters enter.
+    1 <= m <= min(gpk_exact_drop_max_m() = 64, N - 1), otherwise ValueError."""
+    if L.dim() != 3 or L.shape[1] != L.shape[2]:
+        raise ValueError(f"L must be (B, N, N), got {tuple(L.shape)}")
+    B, N, _ = L.shape
+    if z.shape != (B, N):
+        raise ValueError(f"z must be (B, N) = {(B, N)}, got {tuple(z.shape)}")
+    _require_device(L, z)
+    m = int(m)
+    lib = _native.lib()
+    if m < 1 or m > min(lib.gpk_exact_drop_max_m(), N - 1):
+        raise ValueError(f"m must be in 1 .. min(gpk_exact_drop_max_m() = {lib.gpk_exact_drop_max_m()}, N - 1 = "
+                         f"{N - 1}), got {m}")
+    L = L.detach().contiguous().float()
+    z = z.detach().contiguous().float()
+    dev = L.device
+    L2 = torch.empty(B, N - m, N - m, device=dev, dtype=torch.float32)
+    z2 = torch.empty(B, N - m, device=dev, dtype=torch.float32)
+    if B == 0:
+        return L2, z2
+    rc = lib.gpk_exact_drop_f32(L.data_ptr(), z.data_ptr(), B, N, m, L2.data_ptr(), z2.data_ptr(), _stream_ptr(dev))
+    if rc != 0:
+        _native.check(rc, "gpk_exact_drop_f32")
+    return L2, z2
+
+
 @dataclass
 class ExactPosteriorGrad:
     dX: Optional[torch.Tensor]    # (B, N, D)

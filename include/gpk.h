@@ -275,6 +275,45 @@ int gpk_exact_append_perwin_f32(const float* X, const float* L, const float* z, 
                                 float* zout, int* info, void* stream);
 
 /*
+ * Dropping the m oldest observations from a cached exact-GP factor, per window b: from the training
+ * factor L and z = L^{-1}(y - c) of gpk_exact_mll_f32 / gpk_exact_append_f32, the factor and
+ * whitened targets of the last n = N - m points, in O(n^2 m) (nothing is refactored). With
+ *   L = [[L11, 0], [L21, L22]]     z = [z1 ; z2]     U = L21 (n x m)
+ * the kept points' matrix is L22 L22^T + U U^T (whatever jitter the ladder put on the diagonal
+ * included), so L' = chol(L22 L22^T + U U^T), a positive rank-m update, run as rotations: for
+ * column j and t = 0 .. m-1, with rho_t^2 = L_jj^2 + sum_{s<=t} U_js^2,
+ *   cos_t = rho_{t-1} / rho_t    sin_t = U_jt / rho_t
+ *   (L_ij, U_it) <- (cos_t L_ij + sin_t U_it, cos_t U_it - sin_t L_ij)    for every row i > j
+ * and L'_jj = rho_{m-1}; the same rotations on the pairs (z2_j, z1_t) leave z' = L'^{-1}(y[m:] - c)
+ * in z2's place. By the uniqueness of the Cholesky factor these are what gpk_exact_mll_f32 returns
+ * for (X[:, m:], y[:, m:]) at the same total jitter, up to rounding, so every consumer of (L, z)
+ * takes them unchanged, gpk_exact_append_f32 included: drop m, append m keeps N constant and a
+ * look-back window slides over a stream with no factorisation launch. It replaces a refit of the
+ * kept points (gpk_exact_mll_f32, O(n^3)).
+ *
+ * Replaces (reference): nothing upstream. GPyTorch has no counterpart: this is the inverse of
+ * exact_prediction_strategies.py get_fantasy_strategy's low-rank update, for ExactGPModel
+ * (denoising_model/GPModel.py:4-13) on a streaming look-back.
+ *
+ * Neither X, y nor the hyper-parameters enter: there is no hyp argument, no workspace and no
+ * _perwin twin. A positive update has no failing pivot: there is no info; a NaN in window b's
+ * inputs gives NaN in window b's outputs only. One workgroup per window (B on gridDim.x), one
+ * thread per row, workgroup barriers only; m > 32 runs as two exact updates of rank 32 and m - 32,
+ * the second in place on Lout. Memory per call: the outputs only. Fixed order, no atomics, a
+ * window's outputs depend on that window alone: deterministic, and independent of B.
+ *
+ * L : (B, N, N) float, lower factor, upper triangle not read     z : (B, N) float
+ * Limits: 1 <= m <= gpk_exact_drop_max_m() = 64, m < N <= gpk_exact_max_n() = 800
+ * Lout : (B, N - m, N - m) float out, the full square, upper triangle exactly zero
+ * zout : (B, N - m) float out; neither output may overlap L or z (-6 / -7)
+ * Returns -(argument index) for an invalid argument (a rejected m: -5); B == 0 returns 0 and
+ * launches nothing.
+ */
+int gpk_exact_drop_max_m(void);
+int gpk_exact_drop_f32(const float* L, const float* z, int B, int N, int m, float* Lout, float* zout,
+                       void* stream);
+
+/*
  * Shared inducing-point factorisation of the whitened VariationalStrategy:
  *   A    = K_ZZ + jitter (fp32 add, as K_ZZ.add_jitter), then upcast to fp64
  *   L    = psd_safe_cholesky(A) with the fp64 ladder chol_jitter * 10^t
