@@ -1,5 +1,7 @@
 // C-ABI shim: argument validation + dispatch to the gfx950 kernels.
 // Declarations and the reference interfaces each entry point replaces: include/gpk.h.
+#include <initializer_list>
+
 #include "../../include/gpk.h"
 #include "gpk_internal.h"
 #include "gpk_elbo.h"
@@ -17,6 +19,234 @@ size_t gpk_exact_append_ws_floats(int B, int N, int m);
 int gpk_launch_exact_append(const float* X, const float* L, const float* z, const float* hyp, int n_ls,
                             long long hyp_stride, const float* Xn, const float* yn, int B, int N, int m, int D,
                             float jitter, float* ws, float* Lout, float* zout, int* info, hipStream_t stream);
+
+// ---- families of sibling symbols ("One body per family"): the validation ladder and
+//      the launch of an operation are written once, in a static body; the exported symbols forward.
+namespace {
+
+constexpr int kGpkMaxOutputs = 65535;   // gridDim.y
+
+// The code of a refused argument is its position in the caller's own list. A body numbers the
+// arguments by its family's *_batched list; a single-output list is that list without shared_x
+// (position 2, in the families that have it) and without O.
+struct ArgPos {
+  bool batched;           // entered through the *_batched symbol
+  int pos_O;              // position of O in the *_batched list
+  bool shared_x = true;   // that list has shared_x at position 2
+  int operator()(int p) const { return batched ? -p : -(p - (shared_x && p > 2) - (p > pos_O)); }
+};
+
+// Elements between two outputs' inputs: 0 when every output reads the same X (a single-output call).
+static long long x_stride_of(int shared_x, int B, int N, int D) { return shared_x ? 0LL : (long long)B * N * D; }
+
+// Every *_batched_workspace_bytes / *_batched_saved_bytes query: O slices of the single-output size.
+static size_t per_output(int O, size_t single_bytes) {
+  return O < 1 || O > kGpkMaxOutputs ? 0 : (size_t)O * single_bytes;
+}
+
+// Position of the first NULL among the arguments at consecutive positions from `first`, 0 if none.
+static int first_null(int first, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) {
+    if (p == nullptr) return first;
+    ++first;
+  }
+  return 0;
+}
+
+// 1-based index of the first of B, N, M, D outside its range, 0 if none: min_B <= B, 1 <= N <= max_N
+// (0: no upper limit), 1 <= M <= 256, 1 <= D <= 64.
+static int first_bad_size(int B, int N, int M, int D, int min_B, int max_N) {
+  if (B < min_B) return 1;
+  if (N < 1 || (max_N > 0 && N > max_N)) return 2;
+  if (M < 1 || M > 256) return 3;
+  if (D < 1 || D > 64) return 4;
+  return 0;
+}
+
+static bool bad_outputs(int O) { return O < 1 || O > kGpkMaxOutputs; }
+static bool misaligned(const void* p) { return ((size_t)p & 15) != 0; }   // rows are read 16 B at a time
+
+static int kzz_chol(bool batched, const GpkKzzArgs& a, hipStream_t stream) {
+  const ArgPos at{batched, 3, false};
+  if (int p = first_null(1, {a.Z, a.hyp})) return at(p);
+  if (bad_outputs(a.O)) return at(3);
+  if (a.M < 1 || a.M > 256) return at(4);
+  if (a.D < 1 || a.D > 64) return at(5);
+  if (a.max_tries < 0 || a.max_tries > 12) return at(8);
+  if (int p = first_null(9, {a.L, a.Linv, a.info})) return at(p);
+  return gpk_launch_kzz16(a, stream);
+}
+
+static int kzz_backward(bool batched, const GpkKzzGradArgs& a, hipStream_t stream) {
+  const ArgPos at{batched, 6, false};
+  if (int p = first_null(1, {a.dLinv, a.L, a.Linv, a.Z, a.hyp})) return at(p);
+  if (bad_outputs(a.O)) return at(6);
+  if (a.M < 1 || a.M > 256) return at(7);
+  if (a.D < 1 || a.D > 64) return at(8);
+  if (int p = first_null(9, {a.ws, a.dZ, a.dhyp})) return at(p);
+  return gpk_launch_kzz_grad(a, stream);
+}
+
+// Mean-field forward. Its three lists differ by more than shared_x and O (y and ell on the single
+// lists only, saved on two of them), so each symbol names its positions: Z .. hyp, B .. D and
+// mean, var are consecutive from Z, B and mean; 0 = not in the list.
+struct VarFwdPos { int Z, y, O, B, mean, saved; };
+constexpr VarFwdPos kVarFwdSingle{2, 7, 0, 8, 12, 16};    // gpk_variational_f32 (no saved) and _train_f32
+constexpr VarFwdPos kVarFwdBatched{3, 0, 8, 9, 13, 16};   // gpk_variational_batched_f32
+
+// `train`: gpk_variational_train_f32 wants its saved state wherever the shape has a saved-state path
+// (and takes NULL elsewhere); the other two refuse a non-NULL one with B < 1 or without such a path.
+static int var_forward(const VarFwdPos& p, bool train, GpkVarArgs a, int shared_x, int* flags, hipStream_t stream) {
+  if (a.X == nullptr) return -1;
+  if (int q = first_null(p.Z, {a.Z, a.Linv, a.vmean, a.vstd, a.hyp})) return -q;
+  if (bad_outputs(a.O)) return -p.O;
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, 0)) return -(p.B + k - 1);
+  if (int q = first_null(p.mean, {a.mean, a.var})) return -q;
+  if (a.ell != nullptr && a.y == nullptr) return -p.y;
+  if (train ? a.saved == nullptr && gpk_var_saved_bytes(a.B, a.N, a.M, a.D) > 0
+            : a.saved != nullptr && (a.B < 1 || gpk_var_saved_bytes(a.B, a.N, a.M, a.D) == 0))
+    return -p.saved;
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var(a, flags, stream);
+}
+
+// Mean-field adjoint: gpk_variational_adjoint_f32 has no saved argument, _saved_f32 requires it,
+// _batched_f32 takes it or NULL. Z .. gvar, B .. D and workspace .. dpar are consecutive.
+// `no_path` is where a saved state for a shape without a saved-state path is reported: under M by
+// _saved_f32, under saved by _batched_f32.
+struct VarAdjPos { int Z, saved, O, B, no_path, workspace; };
+constexpr VarAdjPos kVarAdjSingle{2, 0, 0, 9, 0, 13};         // gpk_variational_adjoint_f32
+constexpr VarAdjPos kVarAdjSaved{2, 9, 0, 10, 12, 14};        // gpk_variational_adjoint_saved_f32
+constexpr VarAdjPos kVarAdjBatched{3, 10, 11, 12, 10, 16};    // gpk_variational_adjoint_batched_f32
+
+static int var_adjoint(const VarAdjPos& p, bool need_saved, GpkVarAdjArgs a, int shared_x, hipStream_t stream) {
+  if (a.X == nullptr) return -1;
+  if (int q = first_null(p.Z, {a.Z, a.Linv, a.vmean, a.vstd, a.hyp, a.gmean, a.gvar})) return -q;
+  if (need_saved && a.saved == nullptr) return -p.saved;
+  if (bad_outputs(a.O)) return -p.O;
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 1, 0)) return -(p.B + k - 1);
+  if (a.saved != nullptr && gpk_var_saved_bytes(a.B, a.N, a.M, a.D) == 0) return -p.no_path;
+  if (int q = first_null(p.workspace, {a.ws, a.dX, a.dLinv, a.dZ, a.dpar})) return -q;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_adjoint(a, stream);
+}
+
+// Dense covariance of q(f): phase 1 (A = Linv K_ZX, gpk_variational_cov.hip), then the variational
+// mode of the covariance kernel (gpk_posterior_cov.hip).
+static int var_cov(bool batched, const float* X, int shared_x, const float* Z, const double* Linv,
+                   const float* vstd, const float* hyp, int O, int B, int N, int M, int D, void* workspace,
+                   float* cov, hipStream_t stream) {
+  const ArgPos at{batched, 7};
+  if (X == nullptr) return at(1);
+  if (int p = first_null(3, {Z, Linv, vstd, hyp})) return at(p);
+  if (bad_outputs(O)) return at(7);
+  if (int k = first_bad_size(B, N, M, D, 0, 0)) return at(7 + k);
+  if (workspace == nullptr || misaligned(workspace)) return at(12);
+  if (cov == nullptr) return at(13);
+  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return at(9);
+  if (B == 0) return 0;
+  GpkVarCovArgs a{hyp, X, (const float*)workspace, vstd, B, M, N, D, gpk_post_cov_vstride(N), cov,
+                  x_stride_of(shared_x, B, N, D), (long long)gpk_var_cov_ws_floats(B, N, M)};
+  const int rc = gpk_launch_variational_cov_phase1(a, (float*)workspace, Z, Linv, O, stream);
+  if (rc != 0) return rc;
+  return gpk_launch_variational_cov_phase2(a, O, stream);
+}
+
+// Adjoint of the dense covariance of q(f) (gpk_variational_cov_grad.hip).
+static int var_cov_grad(bool batched, GpkVarCovGradArgs a, int shared_x, hipStream_t stream) {
+  const ArgPos at{batched, 9};
+  if (a.X == nullptr) return at(1);
+  if (int p = first_null(3, {a.Z, a.Linv, a.vstd, a.hyp})) return at(p);
+  if (a.state == nullptr || misaligned(a.state)) return at(7);
+  if (a.gcov == nullptr) return at(8);
+  if (bad_outputs(a.O)) return at(9);
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, kGpkMvnRootMaxN)) return at(9 + k);
+  if (a.ws == nullptr || misaligned(a.ws)) return at(14);
+  if (int p = first_null(15, {a.dX, a.dLinv, a.dZ, a.dpar})) return at(p);
+  if (a.B > 0 && gpk_var_cov_grad_ws_bytes(a.B, a.N, a.M, a.D) == 0) return at(10);
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_cov_grad(a, stream);
+}
+
+// Cholesky q(u): forward, adjoint, KL (gpk_var_chol.hip).
+static int var_chol(bool batched, GpkVarCholArgs a, int shared_x, hipStream_t stream) {
+  const ArgPos at{batched, 8};
+  if (a.X == nullptr) return at(1);
+  if (int p = first_null(3, {a.Z, a.Linv, a.vmean, a.vchol, a.hyp})) return at(p);
+  if (bad_outputs(a.O)) return at(8);
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, 0)) return at(8 + k);
+  if (int p = first_null(13, {a.mean, a.var})) return at(p);
+  // both siblings refuse a misaligned saved; only _batched_f32 also refuses one with B < 1 or for a
+  // shape without a saved state
+  if (a.saved != nullptr &&
+      (misaligned(a.saved) || (batched && (a.B < 1 || gpk_var_chol_saved_bytes(a.B, a.N, a.M, a.D) == 0))))
+    return at(16);
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_chol(a, stream);
+}
+
+static int var_chol_adjoint(bool batched, GpkVarCholAdjArgs a, int shared_x, hipStream_t stream) {
+  const ArgPos at{batched, 11};
+  if (a.X == nullptr) return at(1);
+  if (int p = first_null(3, {a.Z, a.Linv, a.vmean, a.vchol, a.hyp, a.gmean, a.gvar})) return at(p);
+  if (a.saved == nullptr || misaligned(a.saved)) return at(10);
+  if (bad_outputs(a.O)) return at(11);
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, 256)) return at(11 + k);
+  if (a.ws == nullptr || misaligned(a.ws)) return at(16);
+  if (int p = first_null(17, {a.dX, a.dLinv, a.dZ, a.dpar, a.dchol})) return at(p);
+  if (a.B > 0 && gpk_var_chol_adjoint_ws_bytes(a.B, a.N, a.M, a.D) == 0) return at(12);
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_chol_adjoint(a, stream);
+}
+
+static int cholesky_kl(bool batched, const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
+                       float* dm, float* dchol, hipStream_t stream) {
+  const ArgPos at{batched, 3, false};
+  if (int p = first_null(1, {m, chol})) return at(p);
+  if (bad_outputs(O)) return at(3);
+  if (M < 1 || M > 16384) return at(4);
+  if (gkl == nullptr && kl == nullptr) return at(5);
+  if (gkl != nullptr && dm == nullptr) return at(7);
+  if (gkl != nullptr && dchol == nullptr) return at(8);
+  return gpk_launch_chol_kl(m, chol, O, M, kl, gkl, dm, dchol, stream);
+}
+
+// Dense covariance of q(f) for a Cholesky q(u) and its adjoint (gpk_var_chol_cov.hip).
+static int var_chol_cov(bool batched, GpkVarCholCovArgs a, int shared_x, hipStream_t stream) {
+  const ArgPos at{batched, 7};
+  if (a.X == nullptr) return at(1);
+  if (int p = first_null(3, {a.Z, a.Linv, a.vchol, a.hyp})) return at(p);
+  if (bad_outputs(a.O)) return at(7);
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, 0)) return at(7 + k);
+  if (a.state == nullptr || misaligned(a.state)) return at(12);
+  if (a.cov == nullptr) return at(13);
+  if (gpk_var_chol_cov_state_bytes(a.B, a.N, a.M) == 0 && a.B > 0) return at(9);
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_chol_cov(a, stream);
+}
+
+static int var_chol_cov_grad(bool batched, GpkVarCholCovGradArgs a, int shared_x, hipStream_t stream) {
+  const ArgPos at{batched, 9};
+  if (a.X == nullptr) return at(1);
+  if (int p = first_null(3, {a.Z, a.Linv, a.vchol, a.hyp})) return at(p);
+  if (a.state == nullptr || misaligned(a.state)) return at(7);
+  if (a.gcov == nullptr) return at(8);
+  if (bad_outputs(a.O)) return at(9);
+  if (int k = first_bad_size(a.B, a.N, a.M, a.D, 0, kGpkMvnRootMaxN)) return at(9 + k);
+  if (a.ws == nullptr || misaligned(a.ws)) return at(14);
+  if (int p = first_null(15, {a.dX, a.dLinv, a.dZ, a.dpar, a.dchol})) return at(p);
+  if (a.B > 0 && gpk_var_chol_cov_grad_ws_bytes(a.B, a.N, a.M, a.D) == 0) return at(10);
+  if (a.B == 0) return 0;
+  a.x_stride = x_stride_of(shared_x, a.B, a.N, a.D);
+  return gpk_launch_var_chol_cov_grad(a, stream);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -270,19 +500,19 @@ int gpk_exact_posterior_grad_f32(const float* X, const float* L, const float* z,
                                              Ns, D, workspace, dX, dy, dXs, dhyp, stream);
 }
 
+// ---- K_ZZ factor and its backward: single-output and multi-output (output o on grid dimension y)
 int gpk_kzz_chol_f64(const float* Z, const float* hyp, int M, int D, float jitter,
                      double chol_jitter, int max_tries, double* L, double* Linv, int* info,
                      void* stream) {
-  if (Z == nullptr) return -1;
-  if (hyp == nullptr) return -2;
-  if (M < 1 || M > 256) return -3;
-  if (D < 1 || D > 64) return -4;
-  if (max_tries < 0 || max_tries > 12) return -7;
-  if (L == nullptr) return -8;
-  if (Linv == nullptr) return -9;
-  if (info == nullptr) return -10;
-  GpkKzzArgs a{Z, hyp, M, D, jitter, chol_jitter, max_tries, L, Linv, info};
-  return gpk_launch_kzz16(a, (hipStream_t)stream);
+  return kzz_chol(false, GpkKzzArgs{Z, hyp, M, D, jitter, chol_jitter, max_tries, L, Linv, info, 1},
+                  (hipStream_t)stream);
+}
+
+int gpk_kzz_chol_f64_batched(const float* Z, const float* hyp, int O, int M, int D, float jitter,
+                             double chol_jitter, int max_tries, double* L, double* Linv, int* info,
+                             void* stream) {
+  return kzz_chol(true, GpkKzzArgs{Z, hyp, M, D, jitter, chol_jitter, max_tries, L, Linv, info, O},
+                  (hipStream_t)stream);
 }
 
 size_t gpk_kzz_backward_workspace_bytes(int M, int D) {
@@ -290,21 +520,22 @@ size_t gpk_kzz_backward_workspace_bytes(int M, int D) {
   return gpk_kzz_grad_ws_bytes(M, D);
 }
 
+size_t gpk_kzz_backward_batched_workspace_bytes(int O, int M, int D) {
+  return per_output(O, gpk_kzz_backward_workspace_bytes(M, D));
+}
+
 int gpk_kzz_backward_f64(const double* dLinv, const double* L, const double* Linv, const float* Z,
                          const float* hyp, int M, int D, void* workspace, float* dZ, float* dhyp,
                          void* stream) {
-  if (dLinv == nullptr) return -1;
-  if (L == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (Z == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (M < 1 || M > 256) return -6;
-  if (D < 1 || D > 64) return -7;
-  if (workspace == nullptr) return -8;
-  if (dZ == nullptr) return -9;
-  if (dhyp == nullptr) return -10;
-  GpkKzzGradArgs a{dLinv, L, Linv, Z, hyp, M, D, workspace, dZ, dhyp};
-  return gpk_launch_kzz_grad(a, (hipStream_t)stream);
+  return kzz_backward(false, GpkKzzGradArgs{dLinv, L, Linv, Z, hyp, M, D, workspace, dZ, dhyp, 1},
+                      (hipStream_t)stream);
+}
+
+int gpk_kzz_backward_f64_batched(const double* dLinv, const double* L, const double* Linv,
+                                 const float* Z, const float* hyp, int O, int M, int D, void* workspace,
+                                 float* dZ, float* dhyp, void* stream) {
+  return kzz_backward(true, GpkKzzGradArgs{dLinv, L, Linv, Z, hyp, M, D, workspace, dZ, dhyp, O},
+                      (hipStream_t)stream);
 }
 
 int gpk_gauss_ell_f32(const float* y, const float* mean, const float* var, const float* noise, int R,
@@ -412,88 +643,48 @@ int gpk_record_check(const int* info, int n, const float* in0, long long n0, con
                             kind == 2, (hipStream_t)stream);
 }
 
+// ---- mean-field variational forward and adjoint
 int gpk_variational_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
                         const float* vstd, const float* hyp, const float* y, int B, int N, int M,
                         int D, float* mean, float* var, float* ell, int* flags, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (B < 0) return -8;
-  if (N < 1) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (mean == nullptr) return -12;
-  if (var == nullptr) return -13;
-  if (ell != nullptr && y == nullptr) return -7;
-  if (B == 0) return 0;
   GpkVarArgs a{X, Z, Linv, vmean, vstd, hyp, y, B, N, M, D, mean, var, ell};
-  return gpk_launch_var(a, flags, (hipStream_t)stream);
+  return var_forward(kVarFwdSingle, false, a, 1, flags, (hipStream_t)stream);
 }
 
 size_t gpk_variational_saved_bytes(int B, int N, int M, int D) {
   if (B < 1 || N < 1 || M < 1 || M > 256 || D < 1 || D > 64) return 0;
   return gpk_var_saved_bytes(B, N, M, D);
 }
+
 int gpk_variational_train_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
                               const float* vstd, const float* hyp, const float* y, int B, int N, int M,
                               int D, float* mean, float* var, float* ell, int* flags, void* saved,
                               void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (B < 0) return -8;
-  if (N < 1) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (mean == nullptr) return -12;
-  if (var == nullptr) return -13;
-  if (ell != nullptr && y == nullptr) return -7;
-  if (saved == nullptr && gpk_var_saved_bytes(B, N, M, D) > 0) return -16;
-  if (B == 0) return 0;
   GpkVarArgs a{X, Z, Linv, vmean, vstd, hyp, y, B, N, M, D, mean, var, ell, (float*)saved};
-  return gpk_launch_var(a, flags, (hipStream_t)stream);
+  return var_forward(kVarFwdSingle, true, a, 1, flags, (hipStream_t)stream);
 }
+
+int gpk_variational_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
+                                const float* vmean, const float* vstd, const float* hyp, int O, int B,
+                                int N, int M, int D, float* mean, float* var, int* flags, void* saved,
+                                void* stream) {
+  GpkVarArgs a{X, Z, Linv, vmean, vstd, hyp, nullptr, B, N, M, D, mean, var, nullptr, (float*)saved, O};
+  return var_forward(kVarFwdBatched, false, a, shared_x, flags, (hipStream_t)stream);
+}
+
+size_t gpk_variational_adjoint_workspace_bytes(int B, int N, int M, int D) {
+  if (B < 1 || N < 1 || M < 1 || M > 256 || D < 1 || D > 64) return 0;
+  return gpk_var_adjoint_ws_bytes(B, N, M, D);
+}
+
 size_t gpk_variational_adjoint_saved_workspace_bytes(int B, int N, int M, int D) {
   if (B < 1 || N < 1 || M < 1 || M > 256 || D < 1 || D > 64) return 0;
   return gpk_var_adjoint_saved_ws_bytes(B, N, M, D);
 }
-int gpk_variational_adjoint_saved_f32(const float* X, const float* Z, const double* Linv,
-                                      const float* vmean, const float* vstd, const float* hyp,
-                                      const float* gmean, const float* gvar, const void* saved, int B,
-                                      int N, int M, int D, void* workspace, float* dX, double* dLinv,
-                                      float* dZ, float* dpar, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (gmean == nullptr) return -7;
-  if (gvar == nullptr) return -8;
-  if (saved == nullptr) return -9;
-  if (B < 1) return -10;
-  if (N < 1) return -11;
-  if (M < 1 || M > 256) return -12;
-  if (D < 1 || D > 64) return -13;
-  if (gpk_var_saved_bytes(B, N, M, D) == 0) return -12;
-  if (workspace == nullptr) return -14;
-  if (dX == nullptr) return -15;
-  if (dLinv == nullptr) return -16;
-  if (dZ == nullptr) return -17;
-  if (dpar == nullptr) return -18;
-  GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar,
-                  (const float*)saved};
-  return gpk_launch_var_adjoint(a, (hipStream_t)stream);
-}
-size_t gpk_variational_adjoint_workspace_bytes(int B, int N, int M, int D) {
-  if (B < 1 || N < 1 || M < 1 || M > 256 || D < 1 || D > 64) return 0;
-  return gpk_var_adjoint_ws_bytes(B, N, M, D);
+
+size_t gpk_variational_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D, int has_saved) {
+  return per_output(O, has_saved ? gpk_variational_adjoint_saved_workspace_bytes(B, N, M, D)
+                                 : gpk_variational_adjoint_workspace_bytes(B, N, M, D));
 }
 
 int gpk_variational_adjoint_f32(const float* X, const float* Z, const double* Linv,
@@ -501,97 +692,18 @@ int gpk_variational_adjoint_f32(const float* X, const float* Z, const double* Li
                                 const float* gmean, const float* gvar, int B, int N, int M, int D,
                                 void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
                                 void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (gmean == nullptr) return -7;
-  if (gvar == nullptr) return -8;
-  if (B < 1) return -9;
-  if (N < 1) return -10;
-  if (M < 1 || M > 256) return -11;
-  if (D < 1 || D > 64) return -12;
-  if (workspace == nullptr) return -13;
-  if (dX == nullptr) return -14;
-  if (dLinv == nullptr) return -15;
-  if (dZ == nullptr) return -16;
-  if (dpar == nullptr) return -17;
   GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar};
-  return gpk_launch_var_adjoint(a, (hipStream_t)stream);
+  return var_adjoint(kVarAdjSingle, false, a, 1, (hipStream_t)stream);
 }
 
-// ---- multi-output (batched) variational chain: output o on grid dimension y of every launch
-constexpr int kGpkMaxOutputs = 65535;   // gridDim.y
-
-int gpk_kzz_chol_f64_batched(const float* Z, const float* hyp, int O, int M, int D, float jitter,
-                             double chol_jitter, int max_tries, double* L, double* Linv, int* info,
-                             void* stream) {
-  if (Z == nullptr) return -1;
-  if (hyp == nullptr) return -2;
-  if (O < 1 || O > kGpkMaxOutputs) return -3;
-  if (M < 1 || M > 256) return -4;
-  if (D < 1 || D > 64) return -5;
-  if (max_tries < 0 || max_tries > 12) return -8;
-  if (L == nullptr) return -9;
-  if (Linv == nullptr) return -10;
-  if (info == nullptr) return -11;
-  GpkKzzArgs a{Z, hyp, M, D, jitter, chol_jitter, max_tries, L, Linv, info, O};
-  return gpk_launch_kzz16(a, (hipStream_t)stream);
-}
-
-size_t gpk_kzz_backward_batched_workspace_bytes(int O, int M, int D) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_kzz_backward_workspace_bytes(M, D);
-}
-
-int gpk_kzz_backward_f64_batched(const double* dLinv, const double* L, const double* Linv,
-                                 const float* Z, const float* hyp, int O, int M, int D, void* workspace,
-                                 float* dZ, float* dhyp, void* stream) {
-  if (dLinv == nullptr) return -1;
-  if (L == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (Z == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (O < 1 || O > kGpkMaxOutputs) return -6;
-  if (M < 1 || M > 256) return -7;
-  if (D < 1 || D > 64) return -8;
-  if (workspace == nullptr) return -9;
-  if (dZ == nullptr) return -10;
-  if (dhyp == nullptr) return -11;
-  GpkKzzGradArgs a{dLinv, L, Linv, Z, hyp, M, D, workspace, dZ, dhyp, O};
-  return gpk_launch_kzz_grad(a, (hipStream_t)stream);
-}
-
-int gpk_variational_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
-                                const float* vmean, const float* vstd, const float* hyp, int O, int B,
-                                int N, int M, int D, float* mean, float* var, int* flags, void* saved,
-                                void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vmean == nullptr) return -5;
-  if (vstd == nullptr) return -6;
-  if (hyp == nullptr) return -7;
-  if (O < 1 || O > kGpkMaxOutputs) return -8;
-  if (B < 0) return -9;
-  if (N < 1) return -10;
-  if (M < 1 || M > 256) return -11;
-  if (D < 1 || D > 64) return -12;
-  if (mean == nullptr) return -13;
-  if (var == nullptr) return -14;
-  if (saved != nullptr && (B < 1 || gpk_var_saved_bytes(B, N, M, D) == 0)) return -16;
-  if (B == 0) return 0;
-  GpkVarArgs a{X, Z, Linv, vmean, vstd, hyp, nullptr, B, N, M, D, mean, var, nullptr, (float*)saved, O,
-               shared_x ? 0LL : (long long)B * N * D};
-  return gpk_launch_var(a, flags, (hipStream_t)stream);
-}
-
-size_t gpk_variational_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D, int has_saved) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * (has_saved ? gpk_variational_adjoint_saved_workspace_bytes(B, N, M, D)
-                                : gpk_variational_adjoint_workspace_bytes(B, N, M, D));
+int gpk_variational_adjoint_saved_f32(const float* X, const float* Z, const double* Linv,
+                                      const float* vmean, const float* vstd, const float* hyp,
+                                      const float* gmean, const float* gvar, const void* saved, int B,
+                                      int N, int M, int D, void* workspace, float* dX, double* dLinv,
+                                      float* dZ, float* dpar, void* stream) {
+  GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar,
+                  (const float*)saved};
+  return var_adjoint(kVarAdjSaved, true, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
@@ -599,127 +711,48 @@ int gpk_variational_adjoint_batched_f32(const float* X, int shared_x, const floa
                                         const float* gmean, const float* gvar, const void* saved, int O,
                                         int B, int N, int M, int D, void* workspace, float* dX,
                                         double* dLinv, float* dZ, float* dpar, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vmean == nullptr) return -5;
-  if (vstd == nullptr) return -6;
-  if (hyp == nullptr) return -7;
-  if (gmean == nullptr) return -8;
-  if (gvar == nullptr) return -9;
-  if (O < 1 || O > kGpkMaxOutputs) return -11;
-  if (B < 1) return -12;
-  if (N < 1) return -13;
-  if (M < 1 || M > 256) return -14;
-  if (D < 1 || D > 64) return -15;
-  if (saved != nullptr && gpk_var_saved_bytes(B, N, M, D) == 0) return -10;
-  if (workspace == nullptr) return -16;
-  if (dX == nullptr) return -17;
-  if (dLinv == nullptr) return -18;
-  if (dZ == nullptr) return -19;
-  if (dpar == nullptr) return -20;
   GpkVarAdjArgs a{X, Z, Linv, vmean, vstd, hyp, gmean, gvar, B, N, M, D, workspace, dX, dLinv, dZ, dpar,
-                  (const float*)saved, O, shared_x ? 0LL : (long long)B * N * D};
-  return gpk_launch_var_adjoint(a, (hipStream_t)stream);
+                  (const float*)saved, O};
+  return var_adjoint(kVarAdjBatched, false, a, shared_x, (hipStream_t)stream);
 }
 
-// ---- dense covariance of q(f): phase 1 (A = Linv K_ZX, gpk_variational_cov.hip), then the
-//      variational mode of the covariance kernel (gpk_posterior_cov.hip)
+// ---- dense covariance of q(f) and its adjoint
 size_t gpk_variational_cov_workspace_bytes(int B, int N, int M) {
   if (!gpk_var_cov_tile_grid_ok(B, N, M)) return 0;
   return gpk_var_cov_ws_floats(B, N, M) * sizeof(float);
 }
 
 size_t gpk_variational_cov_batched_workspace_bytes(int O, int B, int N, int M) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_variational_cov_workspace_bytes(B, N, M);
-}
-
-static int var_cov_run(const float* X, long long x_stride, const float* Z, const double* Linv,
-                       const float* vstd, const float* hyp, int O, int B, int N, int M, int D,
-                       void* workspace, float* cov, hipStream_t stream) {
-  GpkVarCovArgs a{hyp, X, (const float*)workspace, vstd, B, M, N, D, gpk_post_cov_vstride(N), cov, x_stride,
-                  (long long)gpk_var_cov_ws_floats(B, N, M)};
-  const int rc = gpk_launch_variational_cov_phase1(a, (float*)workspace, Z, Linv, O, stream);
-  if (rc != 0) return rc;
-  return gpk_launch_variational_cov_phase2(a, O, stream);
+  return per_output(O, gpk_variational_cov_workspace_bytes(B, N, M));
 }
 
 int gpk_variational_cov_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
                             const float* hyp, int B, int N, int M, int D, void* workspace,
                             float* cov, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vstd == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (B < 0) return -6;
-  if (N < 1) return -7;
-  if (M < 1 || M > 256) return -8;
-  if (D < 1 || D > 64) return -9;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -10;   // A rows are read 16 B at a time
-  if (cov == nullptr) return -11;
-  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return -7;
-  if (B == 0) return 0;
-  return var_cov_run(X, 0, Z, Linv, vstd, hyp, 1, B, N, M, D, workspace, cov, (hipStream_t)stream);
+  return var_cov(false, X, 1, Z, Linv, vstd, hyp, 1, B, N, M, D, workspace, cov, (hipStream_t)stream);
 }
 
 int gpk_variational_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
                                     const float* vstd, const float* hyp, int O, int B, int N, int M,
                                     int D, void* workspace, float* cov, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (O < 1 || O > kGpkMaxOutputs) return -7;
-  if (B < 0) return -8;
-  if (N < 1) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
-  if (cov == nullptr) return -13;
-  if (!gpk_var_cov_tile_grid_ok(B, N, M)) return -9;
-  if (B == 0) return 0;
-  return var_cov_run(X, shared_x ? 0LL : (long long)B * N * D, Z, Linv, vstd, hyp, O, B, N, M, D, workspace,
-                     cov, (hipStream_t)stream);
+  return var_cov(true, X, shared_x, Z, Linv, vstd, hyp, O, B, N, M, D, workspace, cov, (hipStream_t)stream);
 }
 
-// ---- adjoint of the dense covariance of q(f) (gpk_variational_cov_grad.hip)
 size_t gpk_variational_cov_grad_workspace_bytes(int B, int N, int M, int D) {
   return gpk_var_cov_grad_ws_bytes(B, N, M, D);
 }
 
 size_t gpk_variational_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_var_cov_grad_ws_bytes(B, N, M, D);
+  return per_output(O, gpk_var_cov_grad_ws_bytes(B, N, M, D));
 }
 
 int gpk_variational_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vstd,
                                  const float* hyp, const void* state, const float* gcov, int B, int N,
                                  int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
                                  float* dpar, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vstd == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (state == nullptr || ((size_t)state & 15) != 0) return -6;
-  if (gcov == nullptr) return -7;
-  if (B < 0) return -8;
-  if (N < 1 || N > kGpkMvnRootMaxN) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
-  if (dX == nullptr) return -13;
-  if (dLinv == nullptr) return -14;
-  if (dZ == nullptr) return -15;
-  if (dpar == nullptr) return -16;
-  if (B > 0 && gpk_var_cov_grad_ws_bytes(B, N, M, D) == 0) return -8;
-  if (B == 0) return 0;
   GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, 1, 0LL, workspace,
                       dX, dLinv, dZ, dpar};
-  return gpk_launch_var_cov_grad(a, (hipStream_t)stream);
+  return var_cov_grad(false, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
@@ -727,87 +760,41 @@ int gpk_variational_cov_grad_batched_f32(const float* X, int shared_x, const flo
                                          const float* gcov, int O, int B, int N, int M, int D,
                                          void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
                                          void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vstd == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (state == nullptr || ((size_t)state & 15) != 0) return -7;
-  if (gcov == nullptr) return -8;
-  if (O < 1 || O > kGpkMaxOutputs) return -9;
-  if (B < 0) return -10;
-  if (N < 1 || N > kGpkMvnRootMaxN) return -11;
-  if (M < 1 || M > 256) return -12;
-  if (D < 1 || D > 64) return -13;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
-  if (dX == nullptr) return -15;
-  if (dLinv == nullptr) return -16;
-  if (dZ == nullptr) return -17;
-  if (dpar == nullptr) return -18;
-  if (B > 0 && gpk_var_cov_grad_ws_bytes(B, N, M, D) == 0) return -10;
-  if (B == 0) return 0;
-  GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, O,
-                      shared_x ? 0LL : (long long)B * N * D, workspace, dX, dLinv, dZ, dpar};
-  return gpk_launch_var_cov_grad(a, (hipStream_t)stream);
+  GpkVarCovGradArgs a{X, Z, Linv, vstd, hyp, (const float*)state, gcov, B, N, M, D, O, 0LL, workspace,
+                      dX, dLinv, dZ, dpar};
+  return var_cov_grad(true, a, shared_x, (hipStream_t)stream);
 }
 
+// ---- Cholesky q(u)
 size_t gpk_variational_chol_saved_bytes(int B, int N, int M, int D) {
   return gpk_var_chol_saved_bytes(B, N, M, D);
+}
+
+size_t gpk_variational_chol_batched_saved_bytes(int O, int B, int N, int M, int D) {
+  return per_output(O, gpk_var_chol_saved_bytes(B, N, M, D));
 }
 
 int gpk_variational_chol_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
                              const float* vchol, const float* hyp, int B, int N, int M, int D, float* mean,
                              float* var, int* flags, void* saved, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vchol == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (B < 0) return -7;
-  if (N < 1) return -8;
-  if (M < 1 || M > 256) return -9;
-  if (D < 1 || D > 64) return -10;
-  if (mean == nullptr) return -11;
-  if (var == nullptr) return -12;
-  if (saved != nullptr && ((size_t)saved & 15) != 0) return -14;
-  if (B == 0) return 0;
   GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved, 1, 0LL};
-  return gpk_launch_var_chol(a, (hipStream_t)stream);
-}
-
-size_t gpk_variational_chol_batched_saved_bytes(int O, int B, int N, int M, int D) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_var_chol_saved_bytes(B, N, M, D);
+  return var_chol(false, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_chol_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
                                      const float* vmean, const float* vchol, const float* hyp, int O, int B,
                                      int N, int M, int D, float* mean, float* var, int* flags, void* saved,
                                      void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vmean == nullptr) return -5;
-  if (vchol == nullptr) return -6;
-  if (hyp == nullptr) return -7;
-  if (O < 1 || O > kGpkMaxOutputs) return -8;
-  if (B < 0) return -9;
-  if (N < 1) return -10;
-  if (M < 1 || M > 256) return -11;
-  if (D < 1 || D > 64) return -12;
-  if (mean == nullptr) return -13;
-  if (var == nullptr) return -14;
-  if (saved != nullptr && (((size_t)saved & 15) != 0 || B < 1 || gpk_var_chol_saved_bytes(B, N, M, D) == 0))
-    return -16;
-  if (B == 0) return 0;
-  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved, O,
-                   shared_x ? 0LL : (long long)B * N * D};
-  return gpk_launch_var_chol(a, (hipStream_t)stream);
+  GpkVarCholArgs a{X, Z, Linv, vmean, vchol, hyp, B, N, M, D, mean, var, flags, (float*)saved, O, 0LL};
+  return var_chol(true, a, shared_x, (hipStream_t)stream);
 }
 
 size_t gpk_variational_chol_adjoint_workspace_bytes(int B, int N, int M, int D) {
   return gpk_var_chol_adjoint_ws_bytes(B, N, M, D);
+}
+
+size_t gpk_variational_chol_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D) {
+  return per_output(O, gpk_var_chol_adjoint_ws_bytes(B, N, M, D));
 }
 
 int gpk_variational_chol_adjoint_f32(const float* X, const float* Z, const double* Linv, const float* vmean,
@@ -815,35 +802,9 @@ int gpk_variational_chol_adjoint_f32(const float* X, const float* Z, const doubl
                                      const float* gvar, const void* saved, int B, int N, int M, int D,
                                      void* workspace, float* dX, double* dLinv, float* dZ, float* dpar,
                                      float* dchol, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vmean == nullptr) return -4;
-  if (vchol == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (gmean == nullptr) return -7;
-  if (gvar == nullptr) return -8;
-  if (saved == nullptr || ((size_t)saved & 15) != 0) return -9;
-  if (B < 0) return -10;
-  if (N < 1 || N > 256) return -11;
-  if (M < 1 || M > 256) return -12;
-  if (D < 1 || D > 64) return -13;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
-  if (dX == nullptr) return -15;
-  if (dLinv == nullptr) return -16;
-  if (dZ == nullptr) return -17;
-  if (dpar == nullptr) return -18;
-  if (dchol == nullptr) return -19;
-  if (B > 0 && gpk_var_chol_adjoint_ws_bytes(B, N, M, D) == 0) return -10;
-  if (B == 0) return 0;
   GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
                       dX, dLinv, dZ, dpar, dchol, 1, 0LL};
-  return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
-}
-
-size_t gpk_variational_chol_adjoint_batched_workspace_bytes(int O, int B, int N, int M, int D) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_var_chol_adjoint_ws_bytes(B, N, M, D);
+  return var_chol_adjoint(false, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_chol_adjoint_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
@@ -852,83 +813,42 @@ int gpk_variational_chol_adjoint_batched_f32(const float* X, int shared_x, const
                                              int B, int N, int M, int D, void* workspace, float* dX,
                                              double* dLinv, float* dZ, float* dpar, float* dchol,
                                              void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vmean == nullptr) return -5;
-  if (vchol == nullptr) return -6;
-  if (hyp == nullptr) return -7;
-  if (gmean == nullptr) return -8;
-  if (gvar == nullptr) return -9;
-  if (saved == nullptr || ((size_t)saved & 15) != 0) return -10;
-  if (O < 1 || O > kGpkMaxOutputs) return -11;
-  if (B < 0) return -12;
-  if (N < 1 || N > 256) return -13;
-  if (M < 1 || M > 256) return -14;
-  if (D < 1 || D > 64) return -15;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -16;
-  if (dX == nullptr) return -17;
-  if (dLinv == nullptr) return -18;
-  if (dZ == nullptr) return -19;
-  if (dpar == nullptr) return -20;
-  if (dchol == nullptr) return -21;
-  if (B > 0 && gpk_var_chol_adjoint_ws_bytes(B, N, M, D) == 0) return -12;
-  if (B == 0) return 0;
   GpkVarCholAdjArgs a{X, Z, Linv, vmean, vchol, hyp, gmean, gvar, (const float*)saved, B, N, M, D, workspace,
-                      dX, dLinv, dZ, dpar, dchol, O, shared_x ? 0LL : (long long)B * N * D};
-  return gpk_launch_var_chol_adjoint(a, (hipStream_t)stream);
+                      dX, dLinv, dZ, dpar, dchol, O, 0LL};
+  return var_chol_adjoint(true, a, shared_x, (hipStream_t)stream);
 }
 
-// ---- dense covariance of q(f) for a Cholesky q(u) and its adjoint (gpk_var_chol_cov.hip)
+int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,
+                        float* dchol, void* stream) {
+  return cholesky_kl(false, m, chol, 1, M, kl, gkl, dm, dchol, (hipStream_t)stream);
+}
+
+int gpk_cholesky_kl_batched_f32(const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
+                                float* dm, float* dchol, void* stream) {
+  return cholesky_kl(true, m, chol, O, M, kl, gkl, dm, dchol, (hipStream_t)stream);
+}
+
+// ---- dense covariance of q(f) for a Cholesky q(u) and its adjoint
 size_t gpk_variational_chol_cov_workspace_bytes(int B, int N, int M) {
   return gpk_var_chol_cov_state_bytes(B, N, M);
 }
 
 size_t gpk_variational_chol_cov_batched_workspace_bytes(int O, int B, int N, int M) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_var_chol_cov_state_bytes(B, N, M);
+  return per_output(O, gpk_var_chol_cov_state_bytes(B, N, M));
 }
 
 int gpk_variational_chol_cov_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
                                  const float* hyp, int B, int N, int M, int D, void* workspace, float* cov,
                                  void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vchol == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (B < 0) return -6;
-  if (N < 1) return -7;
-  if (M < 1 || M > 256) return -8;
-  if (D < 1 || D > 64) return -9;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -10;   // panel rows are read 16 B at a time
-  if (cov == nullptr) return -11;
-  if (gpk_var_chol_cov_state_bytes(B, N, M) == 0 && B > 0) return -7;
-  if (B == 0) return 0;
   GpkVarCholCovArgs a{X, Z, Linv, vchol, hyp, B, N, M, D, 1, 0LL, (float*)workspace, cov};
-  return gpk_launch_var_chol_cov(a, (hipStream_t)stream);
+  return var_chol_cov(false, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_chol_cov_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
                                          const float* vchol, const float* hyp, int O, int B, int N, int M,
                                          int D, void* workspace, float* cov, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vchol == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (O < 1 || O > kGpkMaxOutputs) return -7;
-  if (B < 0) return -8;
-  if (N < 1) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
-  if (cov == nullptr) return -13;
-  if (gpk_var_chol_cov_state_bytes(B, N, M) == 0 && B > 0) return -9;
-  if (B == 0) return 0;
-  GpkVarCholCovArgs a{X, Z, Linv, vchol, hyp, B, N, M, D, O, shared_x ? 0LL : (long long)B * N * D,
-                      (float*)workspace, cov};
-  return gpk_launch_var_chol_cov(a, (hipStream_t)stream);
+  GpkVarCholCovArgs a{X, Z, Linv, vchol, hyp, B, N, M, D, O, 0LL, (float*)workspace, cov};
+  return var_chol_cov(true, a, shared_x, (hipStream_t)stream);
 }
 
 size_t gpk_variational_chol_cov_grad_workspace_bytes(int B, int N, int M, int D) {
@@ -936,36 +856,16 @@ size_t gpk_variational_chol_cov_grad_workspace_bytes(int B, int N, int M, int D)
 }
 
 size_t gpk_variational_chol_cov_grad_batched_workspace_bytes(int O, int B, int N, int M, int D) {
-  if (O < 1 || O > kGpkMaxOutputs) return 0;
-  return (size_t)O * gpk_var_chol_cov_grad_ws_bytes(B, N, M, D);
+  return per_output(O, gpk_var_chol_cov_grad_ws_bytes(B, N, M, D));
 }
 
 int gpk_variational_chol_cov_grad_f32(const float* X, const float* Z, const double* Linv, const float* vchol,
                                       const float* hyp, const void* state, const float* gcov, int B, int N,
                                       int M, int D, void* workspace, float* dX, double* dLinv, float* dZ,
                                       float* dpar, float* dchol, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -2;
-  if (Linv == nullptr) return -3;
-  if (vchol == nullptr) return -4;
-  if (hyp == nullptr) return -5;
-  if (state == nullptr || ((size_t)state & 15) != 0) return -6;
-  if (gcov == nullptr) return -7;
-  if (B < 0) return -8;
-  if (N < 1 || N > kGpkMvnRootMaxN) return -9;
-  if (M < 1 || M > 256) return -10;
-  if (D < 1 || D > 64) return -11;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -12;
-  if (dX == nullptr) return -13;
-  if (dLinv == nullptr) return -14;
-  if (dZ == nullptr) return -15;
-  if (dpar == nullptr) return -16;
-  if (dchol == nullptr) return -17;
-  if (B > 0 && gpk_var_chol_cov_grad_ws_bytes(B, N, M, D) == 0) return -8;
-  if (B == 0) return 0;
   GpkVarCholCovGradArgs a{X, Z, Linv, vchol, hyp, (const float*)state, gcov, B, N, M, D, 1, 0LL, workspace,
                           dX, dLinv, dZ, dpar, dchol};
-  return gpk_launch_var_chol_cov_grad(a, (hipStream_t)stream);
+  return var_chol_cov_grad(false, a, 1, (hipStream_t)stream);
 }
 
 int gpk_variational_chol_cov_grad_batched_f32(const float* X, int shared_x, const float* Z, const double* Linv,
@@ -973,52 +873,9 @@ int gpk_variational_chol_cov_grad_batched_f32(const float* X, int shared_x, cons
                                               const float* gcov, int O, int B, int N, int M, int D,
                                               void* workspace, float* dX, double* dLinv, float* dZ,
                                               float* dpar, float* dchol, void* stream) {
-  if (X == nullptr) return -1;
-  if (Z == nullptr) return -3;
-  if (Linv == nullptr) return -4;
-  if (vchol == nullptr) return -5;
-  if (hyp == nullptr) return -6;
-  if (state == nullptr || ((size_t)state & 15) != 0) return -7;
-  if (gcov == nullptr) return -8;
-  if (O < 1 || O > kGpkMaxOutputs) return -9;
-  if (B < 0) return -10;
-  if (N < 1 || N > kGpkMvnRootMaxN) return -11;
-  if (M < 1 || M > 256) return -12;
-  if (D < 1 || D > 64) return -13;
-  if (workspace == nullptr || ((size_t)workspace & 15) != 0) return -14;
-  if (dX == nullptr) return -15;
-  if (dLinv == nullptr) return -16;
-  if (dZ == nullptr) return -17;
-  if (dpar == nullptr) return -18;
-  if (dchol == nullptr) return -19;
-  if (B > 0 && gpk_var_chol_cov_grad_ws_bytes(B, N, M, D) == 0) return -10;
-  if (B == 0) return 0;
-  GpkVarCholCovGradArgs a{X, Z, Linv, vchol, hyp, (const float*)state, gcov, B, N, M, D, O,
-                          shared_x ? 0LL : (long long)B * N * D, workspace, dX, dLinv, dZ, dpar, dchol};
-  return gpk_launch_var_chol_cov_grad(a, (hipStream_t)stream);
-}
-
-int gpk_cholesky_kl_f32(const float* m, const float* chol, int M, float* kl, const float* gkl, float* dm,
-                        float* dchol, void* stream) {
-  if (m == nullptr) return -1;
-  if (chol == nullptr) return -2;
-  if (M < 1 || M > 16384) return -3;
-  if (gkl == nullptr && kl == nullptr) return -4;
-  if (gkl != nullptr && dm == nullptr) return -6;
-  if (gkl != nullptr && dchol == nullptr) return -7;
-  return gpk_launch_chol_kl(m, chol, 1, M, kl, gkl, dm, dchol, (hipStream_t)stream);
-}
-
-int gpk_cholesky_kl_batched_f32(const float* m, const float* chol, int O, int M, float* kl, const float* gkl,
-                                float* dm, float* dchol, void* stream) {
-  if (m == nullptr) return -1;
-  if (chol == nullptr) return -2;
-  if (O < 1 || O > kGpkMaxOutputs) return -3;
-  if (M < 1 || M > 16384) return -4;
-  if (gkl == nullptr && kl == nullptr) return -5;
-  if (gkl != nullptr && dm == nullptr) return -7;
-  if (gkl != nullptr && dchol == nullptr) return -8;
-  return gpk_launch_chol_kl(m, chol, O, M, kl, gkl, dm, dchol, (hipStream_t)stream);
+  GpkVarCholCovGradArgs a{X, Z, Linv, vchol, hyp, (const float*)state, gcov, B, N, M, D, O, 0LL, workspace,
+                          dX, dLinv, dZ, dpar, dchol};
+  return var_chol_cov_grad(true, a, shared_x, (hipStream_t)stream);
 }
 
 int gpk_mvn_root_max_n(void) { return kGpkMvnRootMaxN; }

@@ -113,6 +113,32 @@ def _exact_name(base: str, stride: int) -> str:
     return f"gpk_exact_{base}_perwin_f32" if stride else f"gpk_exact_{base}_f32"
 
 
+def _exact_prologue(X, L, z, hyper, Xs, xs: str = "Xs", ns: str = "Ns", others=(), check=None,
+                    layout_first: bool = False):
+    """The shared head of the exact ops that run from a cached factor: shape checks of X, the second
+    input set ``Xs`` (named ``xs``, (B, ``ns``, D)), L and z; ``check(B, N, D, n_ls)`` for the op's own
+    checks (``n_ls`` only with ``layout_first``: the hyper layout is read before the device check,
+    otherwise after the tensors are made contiguous); the device check of these and ``others``.
+    -> (X, L, z, hyper, Xs) detached, contiguous, float32, and (B, N, D, n_ls, hyp_stride)."""
+    if X.dim() != 3 or Xs.dim() != 3:
+        raise ValueError(f"X and {xs} must be (B, N, D) and (B, {ns}, D)")
+    B, N, D = X.shape
+    if Xs.shape[0] != B or Xs.shape[2] != D:
+        raise ValueError(f"{xs} must be (B, {ns}, D) = ({B}, {ns}, {D}), got {tuple(Xs.shape)}")
+    if L.shape != (B, N, N) or z.shape != (B, N):
+        raise ValueError("L / z do not match X")
+    n_ls = stride = None
+    if layout_first:
+        hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
+    if check is not None:
+        check(B, N, D, n_ls)
+    _require_device(X, L, z, hyper, Xs, *others)
+    X, Xs, L, z = (t.detach().contiguous().float() for t in (X, Xs, L, z))
+    if not layout_first:
+        hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
+    return X, L, z, hyper, Xs, (B, N, D, n_ls, stride)
+
+
 @dataclass
 class ExactMLLOut:
     mll: torch.Tensor            # (B,)
@@ -233,21 +259,9 @@ def exact_posterior(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: to
     ``L`` and ``z = L^{-1}(y - c)`` of ``exact_mll`` (one gfx950 kernel launch, see
     include/gpk.h::gpk_exact_posterior_f32). ``hyper`` is the exact path's device vector, or
     (B, 3 + n_ls) with one row per window."""
-    if X.dim() != 3 or Xs.dim() != 3:
-        raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
-    B, N, D = X.shape
-    if Xs.shape[0] != B or Xs.shape[2] != D:
-        raise ValueError(f"Xs must be (B, Ns, D) = ({B}, Ns, {D}), got {tuple(Xs.shape)}")
-    if L.shape != (B, N, N) or z.shape != (B, N):
-        raise ValueError("L / z do not match X")
-    _require_device(X, L, z, hyper, Xs)
-    X = X.detach().contiguous().float()
-    Xs = Xs.detach().contiguous().float()
-    L = L.detach().contiguous().float()
-    z = z.detach().contiguous().float()
+    X, L, z, hyper, Xs, (B, N, D, n_ls, stride) = _exact_prologue(X, L, z, hyper, Xs)
     Ns = Xs.shape[1]
     dev = X.device
-    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     mean = torch.empty(B, Ns, device=dev, dtype=torch.float32)
     var = torch.empty(B, Ns, device=dev, dtype=torch.float32)
     rc = _native.lib().gpk_exact_posterior_perwin_f32(
@@ -272,21 +286,9 @@ def exact_posterior_cov(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper
     launches of one C-ABI call, see include/gpk.h::gpk_exact_posterior_cov_f32). The V
     workspace (B * N * Ns floats) lives only for the call, unless ``return_state``:
     -> (ExactPosteriorCov, workspace), the saved state ``exact_posterior_grad`` runs from."""
-    if X.dim() != 3 or Xs.dim() != 3:
-        raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
-    B, N, D = X.shape
-    if Xs.shape[0] != B or Xs.shape[2] != D:
-        raise ValueError(f"Xs must be (B, Ns, D) = ({B}, Ns, {D}), got {tuple(Xs.shape)}")
-    if L.shape != (B, N, N) or z.shape != (B, N):
-        raise ValueError("L / z do not match X")
-    _require_device(X, L, z, hyper, Xs)
-    X = X.detach().contiguous().float()
-    Xs = Xs.detach().contiguous().float()
-    L = L.detach().contiguous().float()
-    z = z.detach().contiguous().float()
+    X, L, z, hyper, Xs, (B, N, D, n_ls, stride) = _exact_prologue(X, L, z, hyper, Xs)
     Ns = Xs.shape[1]
     dev = X.device
-    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     lib = _native.lib()
     nbytes = lib.gpk_exact_posterior_cov_workspace_bytes(B, N, Ns)
     if nbytes == 0 and B > 0 and Ns > 0:
@@ -314,24 +316,14 @@ def exact_append(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hyper: torch
     ``jitter`` is added to the diagonal of the Schur complement beside the noise: one rung of the
     jitter ladder, which the caller runs (``info[b] > 0``: window b did not factor). ``hyper`` is
     the exact path's device vector, or (B, 3 + n_ls) with one row per window."""
-    if X.dim() != 3 or Xn.dim() != 3:
-        raise ValueError("X and Xn must be (B, N, D) and (B, m, D)")
-    B, N, D = X.shape
-    if Xn.shape[0] != B or Xn.shape[2] != D:
-        raise ValueError(f"Xn must be (B, m, D) = ({B}, m, {D}), got {tuple(Xn.shape)}")
+    def check_yn(B, N, D, _):
+        if yn.shape != (B, Xn.shape[1]):
+            raise ValueError(f"yn must be (B, m) = {(B, Xn.shape[1])}, got {tuple(yn.shape)}")
+
+    X, L, z, hyper, Xn, (B, N, D, n_ls, stride) = _exact_prologue(X, L, z, hyper, Xn, "Xn", "m", (yn,), check_yn)
     m = Xn.shape[1]
-    if L.shape != (B, N, N) or z.shape != (B, N):
-        raise ValueError("L / z do not match X")
-    if yn.shape != (B, m):
-        raise ValueError(f"yn must be (B, m) = {(B, m)}, got {tuple(yn.shape)}")
-    _require_device(X, L, z, hyper, Xn, yn)
-    X = X.detach().contiguous().float()
-    Xn = Xn.detach().contiguous().float()
     yn = yn.detach().contiguous().float()
-    L = L.detach().contiguous().float()
-    z = z.detach().contiguous().float()
     dev = X.device
-    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
     lib = _native.lib()
     nbytes = lib.gpk_exact_append_workspace_bytes(B, N, m)
     if nbytes == 0 and B > 0:
@@ -399,28 +391,21 @@ def exact_posterior_grad(X: torch.Tensor, L: torch.Tensor, z: torch.Tensor, hype
     matrix), each optional, and the forward's workspace ``state`` returns the gradients with
     respect to the training inputs and targets, the test inputs and, per window, the packed
     hyper-parameters. 1 <= N, Ns <= 256, D <= 64. The workspace lives only for the call."""
-    if X.dim() != 3 or Xs.dim() != 3:
-        raise ValueError("X and Xs must be (B, N, D) and (B, Ns, D)")
-    B, N, D = X.shape
-    if Xs.shape[0] != B or Xs.shape[2] != D:
-        raise ValueError(f"Xs must be (B, Ns, D) = ({B}, Ns, {D}), got {tuple(Xs.shape)}")
+    def check_grads(B, N, D, n_ls):
+        Ns = Xs.shape[1]
+        if n_ls not in (1, D):
+            raise ValueError(f"hyper must have 3 + 1 or 3 + D entries per vector, got {hyper.shape[-1]}")
+        if gmean is None and gvar is None and gcov is None:
+            raise ValueError("at least one of gmean, gvar, gcov must be given")
+        for name, g, shape in (("gmean", gmean, (B, Ns)), ("gvar", gvar, (B, Ns)), ("gcov", gcov, (B, Ns, Ns))):
+            if g is not None and tuple(g.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
+
+    X, L, z, hyper, Xs, (B, N, D, n_ls, stride) = _exact_prologue(
+        X, L, z, hyper, Xs, others=(state, *[g for g in (gmean, gvar, gcov) if g is not None]), check=check_grads,
+        layout_first=True)
     Ns = Xs.shape[1]
-    if L.shape != (B, N, N) or z.shape != (B, N):
-        raise ValueError("L / z do not match X")
-    hyper, n_ls, stride = _exact_hyper_layout(hyper, B)
-    if n_ls not in (1, D):
-        raise ValueError(f"hyper must have 3 + 1 or 3 + D entries per vector, got {hyper.shape[-1]}")
-    if gmean is None and gvar is None and gcov is None:
-        raise ValueError("at least one of gmean, gvar, gcov must be given")
-    for name, g, shape in (("gmean", gmean, (B, Ns)), ("gvar", gvar, (B, Ns)), ("gcov", gcov, (B, Ns, Ns))):
-        if g is not None and tuple(g.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(g.shape)}")
-    _require_device(X, L, z, hyper, Xs, state, *[g for g in (gmean, gvar, gcov) if g is not None])
     dev = X.device
-    X = X.detach().contiguous().float()
-    Xs = Xs.detach().contiguous().float()
-    L = L.detach().contiguous().float()
-    z = z.detach().contiguous().float()
     hyper = hyper.detach().contiguous().float()
     gmean, gvar, gcov = (g.detach().contiguous().float() if g is not None else None for g in (gmean, gvar, gcov))
     lib = _native.lib()
